@@ -83,7 +83,13 @@ def main():
     ap.add_argument("--chunks", type=int, default=4, help="N > 1: chunks per step (exchange of one overlaps parsing of the next)")
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="gloo = rehearsal of the N>1 flow with ranks sharing one GPU (exchange staged through the host)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last step built as DIR/<name>.npy (float64, under 64 MB in all): a "
+                         "seeded sample of the index's (k-mer, count) entries sorted by k-mer, the count histogram and totals of the "
+                         "whole index. The export turns the index dense, so the side figures under 'extra' then time a dense index")
     args = ap.parse_args()
+    if args.steps < 1 or args.warmup < 0:
+        ap.error("--steps must be at least 1 and --warmup at least 0")
     multi_default = args.gpus > 1 or args.force_dist
     if args.reads is None:
         args.reads = 12_500_000 if args.gpus > 1 else 10_000_000
@@ -290,6 +296,8 @@ def main():
     ctx.profile(False)
 
     local_distinct = idx.local_size()
+    if args.dump_outputs:
+        dump_outputs(args.dump_outputs, idx, rank, world if multi else 1, dist if multi else None)
     if multi:
         cdev = dev if args.backend == "nccl" else torch.device("cpu")
         t = torch.tensor([elapsed], dtype=torch.float64, device=cdev)
@@ -376,6 +384,61 @@ def main():
     ctx.close()
     if multi:
         dist.destroy_process_group()
+
+
+DUMP_SAMPLE_BYTES = 48 << 20     # the sampled entries; the histogram and totals add a few KB
+DUMP_HIST_BINS = 256             # counts 0 .. 254 one bin each, the last bin every count >= 255
+DUMP_SEED = 0x6b6d6572696e64
+
+
+def dump_outputs(out_dir, idx, rank, world, dist):
+    """Writes what the index holds after the last timed step as float64 .npy files (every value exact):
+      kmers_sample.npy   [n, 2 * n_words]  the sampled k-mers, each 64-bit word as (high 32 bits, low 32 bits), sorted by k-mer
+      counts_sample.npy  [n]               their counts
+      count_histogram.npy [256]            distinct k-mers per count over the whole index (last bin: count >= 255)
+      totals.npy         [3]               distinct k-mers, k-mer occurrences (sum of counts), largest count
+    The sample is every entry whose k-mer hashes (seeded) below a threshold set from the global distinct count, so it does
+    not depend on export order or on which rank holds a key; it is cut, in k-mer order, to DUMP_SAMPLE_BYTES."""
+    import numpy as np
+    keys, counts = idx.to_vector()
+    keys = keys.reshape(keys.shape[0], -1)
+    n_words = keys.shape[1]
+    hist = np.bincount(np.minimum(counts, DUMP_HIST_BINS - 1).astype(np.int64), minlength=DUMP_HIST_BINS).astype(np.float64)
+    totals = np.array([keys.shape[0], counts.sum(dtype=np.uint64), counts.max() if counts.size else 0], dtype=np.float64)
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, (hist, totals))
+        hist = sum(p[0] for p in parts)
+        totals = np.array([sum(p[1][0] for p in parts), sum(p[1][1] for p in parts), max(p[1][2] for p in parts)])
+    cap = DUMP_SAMPLE_BYTES // (8 * (2 * n_words + 1))
+    # seeded mix of every word of the key; the top 32 bits against a threshold keep about cap * 0.95 entries in all
+    with np.errstate(over="ignore"):
+        h = np.full(keys.shape[0], DUMP_SEED, dtype=np.uint64)
+        for w in range(n_words):
+            h = (h ^ keys[:, w]) * np.uint64(0x9E3779B97F4A7C15)
+            h ^= h >> np.uint64(29)
+    distinct = int(totals[0])
+    thresh = 1 << 32 if distinct <= cap else int((1 << 32) * cap * 0.95 / distinct)
+    sel = (h >> np.uint64(32)) < np.uint64(thresh)
+    keys, counts = keys[sel], counts[sel]
+    del h, sel
+    if world > 1:
+        parts = [None] * world
+        dist.all_gather_object(parts, (keys, counts))
+        keys = np.concatenate([p[0] for p in parts])
+        counts = np.concatenate([p[1] for p in parts])
+    if rank != 0:
+        return
+    order = np.lexsort(keys.T[::-1])[:cap]
+    keys, counts = keys[order], counts[order]
+    halves = np.empty((keys.shape[0], 2 * n_words), dtype=np.float64)
+    halves[:, 0::2] = keys >> np.uint64(32)
+    halves[:, 1::2] = keys & np.uint64(0xFFFFFFFF)
+    os.makedirs(out_dir, exist_ok=True)
+    np.save(os.path.join(out_dir, "kmers_sample.npy"), halves)
+    np.save(os.path.join(out_dir, "counts_sample.npy"), counts.astype(np.float64))
+    np.save(os.path.join(out_dir, "count_histogram.npy"), hist)
+    np.save(os.path.join(out_dir, "totals.npy"), totals)
 
 
 def launch_ranks(n):

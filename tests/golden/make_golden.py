@@ -15,6 +15,10 @@ What it collects (data only -- expected values and test input files, no code):
   src/io/test/mpi_test_fastq_seq_parse.cpp:446-459 (K=35, DNA5) and
   src/io/test/mpi_test_fasta_seq_parse.cpp:398-403.
 * data/* : the small input files of test/data those tables refer to.
+* ref_hashes.npz : MurmurHash3_x64_128 and util::Hash64WithSeed of the
+  reference's vendored sources compiled as-is (oracle/_ref, `make -C oracle ref`,
+  with the reference's default flags and with -DNDEBUG) on seeded random buffers
+  of 0..64 bytes, stored with the buffers.
 * survey_known_answers.json is written by hand from SURVEY.md section 8(c)
   (values obtained there by running reference-compiled code) and is not
   touched by this script.
@@ -23,6 +27,8 @@ import json
 import os
 import re
 import shutil
+
+import numpy as np
 
 REF = os.environ.get("KMERIND_REFERENCE", "/root/reference")
 HERE = os.path.dirname(os.path.abspath(__file__))
@@ -137,7 +143,43 @@ def alphabet_tables():
     return out
 
 
+def ref_hashes():
+    """-> dict of arrays for ref_hashes.npz: case i hashes data[offsets[i]:offsets[i] + lengths[i]] with seeds[i]"""
+    import ctypes as C
+    import sys
+
+    sys.path.insert(0, os.path.dirname(os.path.dirname(HERE)))
+    from tests import oracle as orc
+    libs = {nd: orc.ref_hash_lib(nd) for nd in (False, True)}
+    if None in libs.values():
+        raise SystemExit("oracle/_ref not built: run `make -C oracle ref` first")
+    rng = np.random.default_rng(11)
+    bufs, lengths, seeds = [], [], []
+    for length in list(range(0, 65)) * 3:
+        buf = rng.integers(0, 256, size=max(length, 1), dtype=np.uint8)
+        for seed in (42, 0, 83):
+            bufs.append(buf)
+            lengths.append(length)
+            seeds.append(seed)
+    offsets = np.cumsum([0] + [b.size for b in bufs[:-1]]).astype(np.int64)
+    data = np.concatenate(bufs)
+    out = {"data": data, "offsets": offsets, "lengths": np.array(lengths, dtype=np.int64),
+           "seeds": np.array(seeds, dtype=np.uint32)}
+    for nd, (mm, fh) in libs.items():
+        sfx = "_ndebug" if nd else ""
+        m = np.zeros((len(bufs), 2), dtype=np.uint64)
+        f = np.zeros(len(bufs), dtype=np.uint64)
+        for i, (o, n, sd) in enumerate(zip(offsets, lengths, seeds)):
+            ptr = data.ctypes.data + int(o)
+            mm(ptr, n, sd, m[i:].ctypes.data)
+            f[i] = fh(C.c_void_p(ptr), n, sd)
+        out["murmur" + sfx] = m
+        out["farm" + sfx] = f
+    return out
+
+
 def main():
+    np.savez(os.path.join(HERE, "ref_hashes.npz"), **ref_hashes())
     with open(os.path.join(HERE, "alphabet_tables.json"), "w") as f:
         json.dump(alphabet_tables(), f)
     with open(os.path.join(HERE, "quality_lut.json"), "w") as f:

@@ -1,6 +1,7 @@
 """Pins the CPU oracle against the reference's own golden vectors:
  * src/common/test/test_kmer.cpp known-answer arrays (tests/golden/kmer_golden.json)
- * vendored MurmurHash3 / FarmHash compiled as-is (oracle/_ref)
+ * vendored MurmurHash3 / FarmHash compiled as-is: their known answers (tests/golden/ref_hashes.npz), and that build
+   itself (oracle/_ref) where it is present
  * TestFileInfo parse-count tables on test/data files (tests/golden/parse_golden.json)
  * SURVEY.md 8(c) known answers obtained from reference-compiled code.
 CPU only."""
@@ -98,15 +99,29 @@ def test_revcomp_is_bitwise_rule():
 
 @pytest.mark.parametrize("ndebug", [False, True])
 def test_hashes_match_reference_build(ndebug):
+    """against the stored answers of the reference build (tests/golden/make_golden.py), and against oracle/_ref itself
+    where the reference checkout was there to build it"""
     ref = orc.ref_hash_lib(ndebug)
-    if ref is None:
-        pytest.skip("oracle/_ref not built (reference checkout absent)")
-    mm, fh = ref
     orc.lib.orc_set_farm_ndebug(int(ndebug))
     try:
-        _check_hashes(mm, fh)
+        _check_stored_hashes(ndebug)
+        if ref is not None:
+            _check_hashes(*ref)
     finally:
         orc.lib.orc_set_farm_ndebug(0)
+
+
+def _check_stored_hashes(ndebug):
+    z = np.load(os.path.join(GOLD, "ref_hashes.npz"))
+    sfx = "_ndebug" if ndebug else ""
+    data, murmur, farm = z["data"], z["murmur" + sfx], z["farm" + sfx]
+    out = np.zeros(2, dtype=np.uint64)
+    assert data.size > 0 and len(z["lengths"]) == 585
+    for i, (o, length, seed) in enumerate(zip(z["offsets"], z["lengths"], z["seeds"])):
+        ptr = data.ctypes.data + int(o)
+        orc.lib.orc_murmur3_x64_128(ptr, int(length), int(seed), out)
+        assert out.tolist() == murmur[i].tolist(), ("murmur", int(length), int(seed))
+        assert orc.lib.orc_farm_hash64_with_seed(ptr, int(length), int(seed)) == int(farm[i]), ("farm", int(length), int(seed))
 
 
 def _check_hashes(mm, fh):
