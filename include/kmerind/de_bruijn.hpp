@@ -153,9 +153,12 @@ class NodeIndex {
     cfg.index_kind = KMI_INDEX_COUNT; cfg.seq_format = KMI_FMT_FASTQ; cfg.seq_filter = KMI_SEQ_ALL; cfg.dist_trans = KMI_DIST_MODEL;
     ::kmerind::check(nullptr, kmi_ctx_create(comm.device, comm.rank(), comm.size(), comm.stream, &ctx));
     ::kmerind::check(ctx, kmi_dbg_create(ctx, &cfg, ValueType::KMI, &g));
-    if (comm.size() > 1) {   // collective: every rank constructs
+    if (comm.size() > 1 && comm.transport.all_to_all_v) {   // the library's collectives over the application's messenger (Index's rule)
+      ::kmerind::check(ctx, kmi_comm_create_transport(ctx, &comm.transport, &rccl));
+    } else if (comm.size() > 1) {   // collective: every rank constructs
       if (comm.unique_id.size() != KMI_COMM_ID_BYTES)
-        throw std::invalid_argument("comm.size() > 1 needs comm.unique_id (kmerind::comm::make_unique_id() on rank 0, handed to every rank)");
+        throw std::invalid_argument("comm.size() > 1 needs comm.unique_id (kmerind::comm::make_unique_id() on rank 0, handed to every rank) or comm.transport; "
+                                    "the de Bruijn engine does not run over comm.exchange");
       ::kmerind::check(ctx, kmi_comm_create(ctx, comm.unique_id.data(), &rccl));
     } else {
       // KMI_FORCE_DIST=1: a one-rank program goes through the code of size() > 1 (a one-rank RCCL communicator), as Index does
@@ -255,7 +258,17 @@ class NodeIndex {
     constexpr uint32_t fmt = SeqParser<const unsigned char *>::KMI;   // FASTQParser (the reference's sample) or FASTAParser
     if (::bliss::index::kmer::detail::format_of(filename) != fmt) throw std::invalid_argument("input filename extension is not supported.");
     ::kmerind::check(ctx, kmi_dbg_set_seq_format(g, fmt));
-    if (rccl && fmt != KMI_FMT_FASTQ) throw std::invalid_argument("the de Bruijn engine over ranks reads FASTQ partitions");
+    if (rccl && fmt == KMI_FMT_FASTA) {
+      // every rank reads its block of the equal split plus look-ahead (k sequence characters behind the block); which record the block
+      // starts in, in which state, and the left neighbour of its first window come from the other blocks' summaries inside the library
+      for (uint64_t look = 1ull << 16;; look *= 16) {
+        ::bliss::index::kmer::detail::FileRange r = ::bliss::index::kmer::detail::read_file_range(filename, comm.rank(), comm.size(), look);
+        int need_more = 0;
+        ::kmerind::check(ctx, kmi_dbg_build_fasta_range_dist_host(g, rccl, r.bytes.data(), r.bytes.size(), r.offset, r.nominal, r.reaches_eof ? 1 : 0,
+                                                                  r.prev_byte, &need_more));
+        if (!need_more) return;
+      }
+    }
     if (rccl) {   // every rank reads its byte range plus look-ahead; the partition is cut at record starts on the device
       for (uint64_t look = 1ull << 20;; look *= 8) {
         ::bliss::index::kmer::detail::FileRange r = ::bliss::index::kmer::detail::read_file_range(filename, comm.rank(), comm.size(), look);

@@ -487,8 +487,9 @@ kmi_status kmi_index_set_owner_ranks(kmi_index *idx, uint32_t nranks);
  * Orientation: the reference keeps a node under whichever strand reached the map first (an order MPI decides); this
  * library keeps the lexicographically smaller strand and turns the edges with it (reverse_complement_edges,
  * de_bruijn_node_trait.hpp:122-124). The node set is the same, and so is every node up to that flip.
- * Input is FASTQ without a sequence filter (what the engine is instantiated with, :96,195); kmi_config.strand,
- * index_kind and dist_trans are not consulted. erase is not provided. */
+ * Input is FASTQ (what the engine is instantiated with, :96,195) or FASTA (kmi_dbg_set_seq_format; the engine is generic over
+ * the sequence type, :108-158), without a sequence filter, on one rank or over ranks; kmi_config.strand, index_kind and dist_trans
+ * are not consulted. */
 typedef struct kmi_dbg kmi_dbg;
 enum { KMI_DBG_EDGE_COUNTS = 0, KMI_DBG_EDGE_EXISTS = 1 };
 #define KMI_DBG_VALUE_WORDS 5 /* a node value in kmi_results.values: uint32_t counts[9] + one uint32_t of padding */
@@ -527,6 +528,14 @@ kmi_status kmi_dbg_find_dist_host(kmi_dbg *g, kmi_comm *comm, const uint64_t *qu
  * look-ahead, cut at record starts on the device, then the collective build) */
 kmi_status kmi_dbg_build_range_dist_host(kmi_dbg *g, kmi_comm *comm, const uint8_t *bytes, size_t n_bytes, uint64_t buffer_offset,
                                          uint64_t nominal_bytes, int reaches_eof, int *need_more);
+/* ... of a FASTA file (FASTAParser), by BYTE RANGE: arguments as kmi_index_build_fasta_range_dist_host. The block's windows need k
+ * sequence characters behind it (the last window's right neighbour), not k - 1; the left neighbour of its first window comes from
+ * the blocks before it (their left carries: the last sequence character, or a record start behind it, in the same one gather as the
+ * block summaries). *need_more = 1 is returned BEFORE anything collective. Then parse in node form, route, one exchange, insert
+ * (collective). Works over a one-rank communicator too. KMI_ERR_INVALID when the graph's sequence format is not FASTA. The union
+ * over the ranks is the graph of the whole file. */
+kmi_status kmi_dbg_build_fasta_range_dist_host(kmi_dbg *g, kmi_comm *comm, const uint8_t *bytes, size_t n_bytes, uint64_t buffer_offset,
+                                               uint64_t nominal_bytes, int reaches_eof, int prev_byte, int *need_more);
 /* nodes.erase(keys): the nodes of the query keys (either strand) leave the map with their edge counts (the erase the node map
  * inherits from the distributed map, distributed_unordered_map.hpp:719-779); *n_erased = nodes removed (here / on this rank) */
 kmi_status kmi_dbg_erase_host(kmi_dbg *g, const uint64_t *queries, size_t nq, uint64_t *n_erased);

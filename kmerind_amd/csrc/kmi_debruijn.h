@@ -410,9 +410,10 @@ static kmi_status dbg_parse(kmi_ctx *ctx, const kmi_config *cfg, const uint8_t *
   // the position ids and turns them into edge bytes in a second pass
   if (fasta) {
     // FASTA (the parser is generic over the sequence type, de_bruijn_construct_engine.hpp:108-158): the extract pass over the compacted
-    // character stream looks the neighbours up through the characters' file positions and leaves (k-mer as parsed, edge byte)
-    KMI_TRY(extract_run(ctx, &c, bytes_dev, n_bytes, 0, (uint64_t *)dr, nullptr, (size_t)nt, false, true, &nt, &ns, nullptr, rw, true));
-    if (node_form) KMI_TRY(dbg_edges(ctx, (uint64_t *)dr, (size_t)nt, nullptr, 0, shape, false, true));
+    // character stream looks the neighbours up through the characters' file positions and leaves node form, or (k-mer as parsed,
+    // edge byte); the in-edge of character 0 of a block of a file over ranks is ctx->fa_left_carry
+    KMI_TRY(extract_run(ctx, &c, bytes_dev, n_bytes, 0, (uint64_t *)dr, nullptr, (size_t)nt, false, true, &nt, &ns, nullptr, rw,
+                        node_form ? EDGES_NODE : EDGES_PARSED));
     *recs_out = (uint64_t *)dr; *n_out = nt;
     return KMI_OK;
   }

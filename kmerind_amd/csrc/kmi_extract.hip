@@ -323,8 +323,9 @@ __global__ __launch_bounds__((ExCfg<NW, BITS>::NT)) void fasta_extract_kernel(
     PackedInput in, KShape shape, bool canonical, const uint64_t *__restrict__ ids_by_rank, const uint64_t *__restrict__ out_off,
     uint64_t out_capacity, uint64_t *__restrict__ out_kmers, uint64_t *__restrict__ out_ids, uint32_t *__restrict__ flags,
     uint32_t kstride /* words between the keys of consecutive tuples */, uint32_t istride /* ... between their ids */,
-    const uint8_t *__restrict__ raw_edges = nullptr /* de Bruijn tuples (kmi_debruijn.h): the input bytes; the id slot then takes the edge byte */,
-    uint64_t file_offset = 0) {
+    const uint8_t *__restrict__ raw_edges /* de Bruijn tuples (kmi_debruijn.h): the input bytes; the id slot then takes the edge byte */,
+    uint64_t file_offset, bool node_form /* ... as 1 | edge byte << 32 beside the smaller strand, the edge byte turned with it */,
+    int left_carry /* the raw byte of the sequence character before character 0 (a block of a file over ranks), -1: none */) {
   using Cfg = ExCfg<NW, BITS>;
   __shared__ uint32_t s_eol[Cfg::EOL_DW];
   __shared__ uint32_t s_stream[Cfg::STREAM_DW];
@@ -345,20 +346,26 @@ __global__ __launch_bounds__((ExCfg<NW, BITS>::NT)) void fasta_extract_kernel(
     uint64_t rc[NW], fw[NW], key[NW];
     const uint32_t pos = s_pos[q];
     window_at<Cfg>(s_stream, pos, shape, rc, fw);
-    select_strand<NW>(rc, fw, canonical, key);
+    select_strand<NW>(rc, fw, canonical || (WITH_IDS && raw_edges != nullptr && node_form), key);
     uint64_t idw = 0;
     if (WITH_IDS) {
       idw = ids_by_rank[tile0 + pos];
       if (raw_edges) {   // uniform
         // edge_iterator.hpp:163-177 over the record's characters (EOLs are not characters: NonEOLIter): the characters left and right
         // of the k-mer in its sequence, DNA16 codes, nothing where the sequence ends. Character r of the compacted stream sits at
-        // the file position its id holds (low 40 bits); a set record-start bit at r means r has no left neighbour.
+        // the file position its id holds (low 40 bits); a set record-start bit at r means r has no left neighbour. Character 0's
+        // left neighbour lies before the buffer: the carried byte, if any.
         const uint64_t r = tile0 + pos, rr = r + shape.k;
         const uint32_t *brk = reinterpret_cast<const uint32_t *>(in.eol);
         uint32_t e = 0;
-        if (r > 0 && !((brk[r >> 5] >> (r & 31u)) & 1u)) e |= code_dna16(raw_edges[(ids_by_rank[r - 1] & 0xFFFFFFFFFFull) - file_offset]) << 4;
+        if (!((brk[r >> 5] >> (r & 31u)) & 1u)) {
+          if (r > 0) e |= code_dna16(raw_edges[(ids_by_rank[r - 1] & 0xFFFFFFFFFFull) - file_offset]) << 4;
+          else if (left_carry >= 0) e |= code_dna16((uint32_t)left_carry) << 4;
+        }
         if (rr < in.n_bytes && !((brk[rr >> 5] >> (rr & 31u)) & 1u)) e |= code_dna16(raw_edges[(ids_by_rank[rr] & 0xFFFFFFFFFFull) - file_offset]);
-        idw = e;
+        // node form: reverse_complement_edges (de_bruijn_node_trait.hpp:122-124) when the other strand is kept, as the FASTQ pass does
+        if (node_form && less_words<NW>(rc, fw)) e = (comp_code<4>(e & 0xFu) << 4) | comp_code<4>(e >> 4);
+        idw = node_form ? (1ull | ((uint64_t)e << 32)) : (uint64_t)e;
       }
     }
     if constexpr (WITH_IDS && kRecVec<NW>) {
@@ -965,7 +972,7 @@ kmi_status fastq_scan(kmi_ctx *ctx, const kmi_config *cfg, const uint8_t *bytes_
 template <int NW, int BITS>
 static kmi_status fasta_extract_impl(kmi_ctx *ctx, const kmi_config *cfg, const uint8_t *bytes_dev, size_t n_bytes, KShape shape,
                                      uint64_t file_offset, uint64_t *out_kmers_dev, uint64_t *out_ids_dev, size_t out_capacity,
-                                     bool apply_strand, bool count_only, uint64_t *n_tuples, uint64_t *n_seqs, uint32_t rec_words, bool edges) {
+                                     bool apply_strand, bool count_only, uint64_t *n_tuples, uint64_t *n_seqs, uint32_t rec_words, uint32_t edges) {
   using Cfg = ExCfg<NW, BITS>;
   const uint32_t kstride = rec_words ? rec_words : (uint32_t)NW, istride = rec_words ? rec_words : 1u;
   if (rec_words) out_ids_dev = out_kmers_dev + NW;   // records: the id follows the key words
@@ -990,11 +997,11 @@ static kmi_status fasta_extract_impl(kmi_ctx *ctx, const kmi_config *cfg, const 
     if (out_ids_dev)
       hipLaunchKernelGGL((fasta_extract_kernel<NW, BITS, true>), dim3((unsigned)n_tiles), dim3(Cfg::NT), 0, ctx->stream, in, shape, canonical,
                          fs.ids_by_rank, (const uint64_t *)off, (uint64_t)out_capacity, out_kmers_dev, out_ids_dev, ctx->d_flags, kstride,
-                         istride, edges ? bytes_dev : (const uint8_t *)nullptr, file_offset);
+                         istride, edges ? bytes_dev : (const uint8_t *)nullptr, file_offset, edges == EDGES_NODE, edges ? ctx->fa_left_carry : -1);
     else
       hipLaunchKernelGGL((fasta_extract_kernel<NW, BITS, false>), dim3((unsigned)n_tiles), dim3(Cfg::NT), 0, ctx->stream, in, shape, canonical,
                          (const uint64_t *)nullptr, (const uint64_t *)off, (uint64_t)out_capacity, out_kmers_dev, (uint64_t *)nullptr,
-                         ctx->d_flags, kstride, istride);
+                         ctx->d_flags, kstride, istride, (const uint8_t *)nullptr, (uint64_t)0, false, -1);
   }
   KMI_HIP(ctx, hipGetLastError());
   uint32_t fl[4] = {0, 0, 0, 0};
@@ -1009,7 +1016,7 @@ static kmi_status fasta_extract_impl(kmi_ctx *ctx, const kmi_config *cfg, const 
 
 static kmi_status fasta_extract(kmi_ctx *ctx, const kmi_config *cfg, const uint8_t *bytes_dev, size_t n_bytes, KShape shape,
                                 uint64_t file_offset, uint64_t *out_kmers_dev, uint64_t *out_ids_dev, size_t out_capacity, bool apply_strand,
-                                bool count_only, uint64_t *n_tuples, uint64_t *n_seqs, uint32_t rec_words = 0, bool edges = false) {
+                                bool count_only, uint64_t *n_tuples, uint64_t *n_seqs, uint32_t rec_words = 0, uint32_t edges = EDGES_NONE) {
   KMI_DISPATCH(shape, fasta_extract_impl, ctx, cfg, bytes_dev, n_bytes, shape, file_offset, out_kmers_dev, out_ids_dev, out_capacity,
                apply_strand, count_only, n_tuples, n_seqs, rec_words, edges);
 }
@@ -1044,8 +1051,9 @@ kmi_status extract_count(kmi_ctx *ctx, const kmi_config *cfg, const uint8_t *byt
 
 kmi_status extract_run(kmi_ctx *ctx, const kmi_config *cfg, const uint8_t *bytes_dev, size_t n_bytes,
                        uint64_t file_offset, uint64_t *out_kmers_dev, uint64_t *out_ids_dev, size_t out_capacity,
-                       bool apply_strand, bool scan_done, uint64_t *n_tuples, uint64_t *n_seqs, float *out_quals_dev, uint32_t rec_words, bool edges) {
-  // edges (FASTQ, records): the value word of every record is 1 | edge byte << 32 and the key the smaller strand (kmi_debruijn.h)
+                       bool apply_strand, bool scan_done, uint64_t *n_tuples, uint64_t *n_seqs, float *out_quals_dev, uint32_t rec_words, uint32_t edges) {
+  // edges (records): EDGES_NODE -- the value word of every record is 1 | edge byte << 32 and the key the smaller strand (kmi_debruijn.h);
+  // EDGES_PARSED (FASTA) -- the value word is the edge byte and the key stays as parsed
   // rec_words != 0: out_kmers_dev takes whole records -- key words, id, and with rec_words == n_words + 2 the quality's float
   // bits -- rec_words words per tuple, the layout the multimap insert reads (out_ids_dev is then unused; out_quals_dev beside
   // records of n_words + 1 words takes the qualities as one dense float array)
@@ -1055,11 +1063,12 @@ kmi_status extract_run(kmi_ctx *ctx, const kmi_config *cfg, const uint8_t *bytes
   if ((out_quals_dev && !out_ids_dev && !rec_words) || ((out_quals_dev || rec_words == shape.n_words + 2u) && cfg->seq_format != KMI_FMT_FASTQ))
     return set_err(ctx, KMI_ERR_INVALID, "k-mer qualities need FASTQ input and are produced together with the ids");
   if (edges && rec_words != shape.n_words + 1u) return set_err(ctx, KMI_ERR_INVALID, "edge tuples are records of n_words + 1 words");
-  if (cfg->seq_format == KMI_FMT_FASTA)   // (edges: the value word is the edge byte, the key stays as parsed; dbg_edges makes node form of it)
+  if (cfg->seq_format == KMI_FMT_FASTA)
     return fasta_extract(ctx, cfg, bytes_dev, n_bytes, shape, file_offset, out_kmers_dev, out_ids_dev, out_capacity, apply_strand, false,
                          n_tuples, n_seqs, rec_words, edges);
+  if (edges == EDGES_PARSED) return set_err(ctx, KMI_ERR_INVALID, "FASTQ edge tuples come in node form from the extract pass");
   KMI_DISPATCH(shape, extract_run_impl, ctx, cfg, bytes_dev, n_bytes, shape, file_offset, out_kmers_dev, out_ids_dev, out_quals_dev,
-               out_capacity, apply_strand, scan_done, n_tuples, n_seqs, rec_words, edges);
+               out_capacity, apply_strand, scan_done, n_tuples, n_seqs, rec_words, edges == EDGES_NODE);
 }
 
 // ---------------------------------------------------------------------------

@@ -119,13 +119,34 @@ __device__ __forceinline__ void fa_chunk_masks(const uint8_t *__restrict__ bytes
   hs = ls & hd;
 }
 
-// ---- pass 1: per-tile summaries
+// The left carry of a range (a de Bruijn block's in-edge for the next block, kmi_dbg_build_fasta_range_dist_host): the last event
+// of the range -- its last sequence character or a record start behind it -- as one ordered word, 0 = neither. An event at byte
+// pos orders as 2 pos + 1 (a record start) or 2 pos + 2 (a sequence character: a record start at a line start comes before the
+// line's first character); the word is that order << 8 | the character's raw byte, so the larger word is the later event.
+__device__ __forceinline__ uint32_t fa_carry_word(const FaChunk &c, const uint32_t (&dw)[4], uint32_t chunk0) {
+  uint32_t v = 0;
+  if (c.ev) v = (2u * (chunk0 + 31u - (uint32_t)__builtin_clz(c.ev)) + 1u) << 8;
+  if (c.seq) {
+    const uint32_t q = 31u - (uint32_t)__builtin_clz(c.seq);
+    const uint32_t w = ((2u * (chunk0 + q) + 2u) << 8) | ((dw[q >> 2] >> (8 * (q & 3))) & 0xffu);
+    v = w > v ? w : v;
+  }
+  return v;
+}
+__device__ __forceinline__ uint32_t wave_reduce_max_u32(uint32_t v) {
+#pragma unroll
+  for (int d = kWave / 2; d > 0; d >>= 1) { const uint32_t o = (uint32_t)__shfl_xor((int)v, d, kWave); v = o > v ? o : v; }
+  return v;
+}
+
+// ---- pass 1: per-tile summaries (CARRY: also the left carry of the tile for every state it may be entered in, carry[3 t + state])
+template <bool CARRY>
 __global__ __launch_bounds__((FaCfg::NT)) void fasta_scan_tiles_kernel(const uint8_t *__restrict__ bytes, uint64_t n_bytes, bool first_ls,
-                                                                      FaTileInfo *__restrict__ info) {
+                                                                      FaTileInfo *__restrict__ info, uint32_t *__restrict__ carry) {
   __shared__ uint32_t s_nl[FaCfg::NT / 2 + 2];
   __shared__ uint32_t s_scan[FaCfg::NT / 64 + 2];
-  __shared__ uint32_t s_acc[6];
-  if (threadIdx.x < 6) s_acc[threadIdx.x] = 0;
+  __shared__ uint32_t s_acc[9];
+  if (threadIdx.x < 9) s_acc[threadIdx.x] = 0;
   uint32_t dw[4], eol, ls, hs;
   fa_chunk_masks(bytes, n_bytes, (uint64_t)blockIdx.x * FaCfg::TILE, first_ls, s_nl, dw, eol, ls, hs);
   FaChunk r[3];
@@ -145,21 +166,32 @@ __global__ __launch_bounds__((FaCfg::NT)) void fasta_scan_tiles_kernel(const uin
     }
     ns = wave_reduce_sum(ns); ne = wave_reduce_sum(ne);
     if (lane_id() == 0) { atomicAdd(&s_acc[i0], ns); atomicAdd(&s_acc[3 + i0], ne); }
+    if constexpr (CARRY) {
+      uint32_t cw = 0;
+#pragma unroll
+      for (uint32_t in = 0; in < 3; ++in) cw = (tin == in) ? fa_carry_word(r[in], dw, threadIdx.x * FaCfg::C) : cw;
+      cw = wave_reduce_max_u32(cw);
+      if (lane_id() == 0 && cw) atomicMax(&s_acc[6 + i0], cw);
+    }
   }
   lds_barrier();
   if (threadIdx.x == 0) {
     FaTileInfo ti; ti.map = total;
     for (int i = 0; i < 3; ++i) { ti.nseq[i] = s_acc[i]; ti.nev[i] = s_acc[3 + i]; }
     info[blockIdx.x] = ti;
+    if constexpr (CARRY) for (int i = 0; i < 3; ++i) carry[3 * (uint64_t)blockIdx.x + i] = s_acc[6 + i];
   }
 }
 
 // ---- pass 2: offsets over tiles (same three-step scheme as FASTQ, with map composition)
+// carry (optional): the tiles' left carries of kmi::fasta_scan_tiles_kernel<true> -> per group of 1024 tiles and state the group is
+// entered in, (1 + tile in the group) << 32 | the tile's carry word of its last tile that has one (0: none)
 __global__ __launch_bounds__(1024) void fasta_offsets_reduce_kernel(const FaTileInfo *__restrict__ info, uint64_t n_tiles,
-                                                                   FaTileSum *__restrict__ sums) {
+                                                                   FaTileSum *__restrict__ sums, const uint32_t *__restrict__ carry,
+                                                                   uint64_t *__restrict__ carry_out) {
   __shared__ uint32_t s_scan[1024 / 64 + 2];
-  __shared__ unsigned long long s_acc[6];
-  if (threadIdx.x < 6) s_acc[threadIdx.x] = 0ull;
+  __shared__ unsigned long long s_acc[9];
+  if (threadIdx.x < 9) s_acc[threadIdx.x] = 0ull;
   const uint64_t t = (uint64_t)blockIdx.x * 1024 + threadIdx.x;
   FaTileInfo ti; ti.map = kFaIdentity;
   for (int i = 0; i < 3; ++i) { ti.nseq[i] = 0; ti.nev[i] = 0; }
@@ -174,12 +206,18 @@ __global__ __launch_bounds__(1024) void fasta_offsets_reduce_kernel(const FaTile
     for (uint32_t in = 0; in < 3; ++in) { ns = (tin == in) ? ti.nseq[in] : ns; ne = (tin == in) ? ti.nev[in] : ne; }
     unsigned long long a = wave_reduce_sum((unsigned long long)ns), b = wave_reduce_sum((unsigned long long)ne);
     if (lane_id() == 0) { atomicAdd(&s_acc[i0], a); atomicAdd(&s_acc[3 + i0], b); }
+    if (carry) {   // uniform
+      const uint32_t cw = t < n_tiles ? carry[3 * t + tin] : 0u;
+      const unsigned long long v = cw ? (((unsigned long long)(threadIdx.x + 1u) << 32) | cw) : 0ull;
+      if (v) atomicMax(&s_acc[6 + i0], v);
+    }
   }
   lds_barrier();
   if (threadIdx.x == 0) {
     FaTileSum o; o.map = total;
     for (int i = 0; i < 3; ++i) { o.nseq[i] = s_acc[i]; o.nev[i] = s_acc[3 + i]; }
     sums[blockIdx.x] = o;
+    if (carry) for (int i = 0; i < 3; ++i) carry_out[3 * (uint64_t)blockIdx.x + i] = s_acc[6 + i];
   }
 }
 
@@ -399,12 +437,13 @@ kmi_status fasta_scan(kmi_ctx *ctx, const kmi_config *cfg, const uint8_t *bytes_
   const uint64_t valid_bytes = (part && ctx->fa_part.valid_bytes < n_bytes) ? ctx->fa_part.valid_bytes : (uint64_t)n_bytes;
   {
     ProfScope ps(ctx, "fasta_scan_tiles", n_bytes);
-    hipLaunchKernelGGL(fasta_scan_tiles_kernel, dim3((unsigned)n_tiles), dim3(FaCfg::NT), 0, ctx->stream, bytes_dev, (uint64_t)n_bytes, first_ls,
-                       info);
+    hipLaunchKernelGGL(fasta_scan_tiles_kernel<false>, dim3((unsigned)n_tiles), dim3(FaCfg::NT), 0, ctx->stream, bytes_dev, (uint64_t)n_bytes, first_ls,
+                       info, (uint32_t *)nullptr);
   }
   {
     ProfScope ps(ctx, "fasta_scan_offsets", n_tiles);
-    hipLaunchKernelGGL(fasta_offsets_reduce_kernel, dim3((unsigned)n_blocks), dim3(1024), 0, ctx->stream, (const FaTileInfo *)info, n_tiles, sums);
+    hipLaunchKernelGGL(fasta_offsets_reduce_kernel, dim3((unsigned)n_blocks), dim3(1024), 0, ctx->stream, (const FaTileInfo *)info, n_tiles, sums,
+                       (const uint32_t *)nullptr, (uint64_t *)nullptr);
     hipLaunchKernelGGL(fasta_offsets_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, sums, n_blocks, init_state, ctx->d_totals);
     hipLaunchKernelGGL(fasta_offsets_apply_kernel, dim3((unsigned)n_blocks), dim3(1024), 0, ctx->stream, (const FaTileInfo *)info, n_tiles,
                        (const FaTileSum *)sums, base);
@@ -549,11 +588,13 @@ extern "C" kmi_status kmi_fasta_partition_dev(kmi_ctx *ctx, const uint8_t *bytes
   FaPart *d_parts = (FaPart *)(sums + n_blocks + 1);
   {
     ProfScope ps(ctx, "fasta_scan_tiles", n_bytes);
-    hipLaunchKernelGGL(fasta_scan_tiles_kernel, dim3((unsigned)n_tiles), dim3(FaCfg::NT), 0, ctx->stream, bytes_dev, (uint64_t)n_bytes, true, info);
+    hipLaunchKernelGGL(fasta_scan_tiles_kernel<false>, dim3((unsigned)n_tiles), dim3(FaCfg::NT), 0, ctx->stream, bytes_dev, (uint64_t)n_bytes, true, info,
+                       (uint32_t *)nullptr);
   }
   {
     ProfScope ps(ctx, "fasta_scan_offsets", n_tiles);
-    hipLaunchKernelGGL(fasta_offsets_reduce_kernel, dim3((unsigned)n_blocks), dim3(1024), 0, ctx->stream, (const FaTileInfo *)info, n_tiles, sums);
+    hipLaunchKernelGGL(fasta_offsets_reduce_kernel, dim3((unsigned)n_blocks), dim3(1024), 0, ctx->stream, (const FaTileInfo *)info, n_tiles, sums,
+                       (const uint32_t *)nullptr, (uint64_t *)nullptr);
     hipLaunchKernelGGL(fasta_offsets_scan_kernel, dim3(1), dim3(1024), 0, ctx->stream, sums, n_blocks, (uint32_t)FA_O, ctx->d_totals);
     hipLaunchKernelGGL(fasta_offsets_apply_kernel, dim3((unsigned)n_blocks), dim3(1024), 0, ctx->stream, (const FaTileInfo *)info, n_tiles,
                        (const FaTileSum *)sums, base);
@@ -574,38 +615,65 @@ extern "C" kmi_status kmi_fasta_partition_dev(kmi_ctx *ctx, const uint8_t *bytes
   return KMI_OK;
 }
 
+namespace kmi {
+
+// The line-kind machine over bytes [0, n_bytes) of a FASTA buffer in HBM, as a transfer function (kmi_fasta_block_summary_dev);
+// carry3 (optional): the range's left carry for every state it may be entered in -- KMI_FA_CARRY_PASS (no sequence character and
+// no record start), KMI_FA_CARRY_CUT (a record starts behind the last sequence character, or there is none behind a record start),
+// or KMI_FA_CARRY_BYTE | the raw byte of the last sequence character. Computed beside the tile scan; still one read-back.
+kmi_status fasta_block_summary(kmi_ctx *ctx, const uint8_t *bytes_dev, size_t n_bytes, bool first_ls, uint64_t *out6, uint64_t *carry3) {
+  for (uint32_t in = 0; in < 3; ++in) { out6[2 * in] = in; out6[2 * in + 1] = 0; if (carry3) carry3[in] = KMI_FA_CARRY_PASS; }
+  if (n_bytes == 0) return KMI_OK;
+  KMI_HIP(ctx, hipSetDevice(ctx->device));
+  const uint64_t n_tiles = (n_bytes + FaCfg::TILE - 1) / FaCfg::TILE;
+  const uint64_t n_blocks = (n_tiles + 1023) / 1024;
+  const size_t sums_bytes = (sizeof(FaTileSum) * (n_blocks + 1) + 15) & ~(size_t)15;
+  const size_t gcarry_bytes = carry3 ? sizeof(uint64_t) * 3 * (n_blocks + 1) : 0;
+  void *p;
+  KMI_TRY(ws_get(ctx, WS_TILE_INFO, sizeof(FaTileInfo) * (n_tiles + 1), &p)); FaTileInfo *info = (FaTileInfo *)p;
+  KMI_TRY(ws_get(ctx, WS_MISC, sums_bytes + gcarry_bytes + (carry3 ? sizeof(uint32_t) * 3 * (n_tiles + 1) : 0), &p));
+  FaTileSum *sums = (FaTileSum *)p;
+  uint64_t *gcarry = carry3 ? (uint64_t *)((uint8_t *)p + sums_bytes) : nullptr;
+  uint32_t *tcarry = carry3 ? (uint32_t *)((uint8_t *)p + sums_bytes + gcarry_bytes) : nullptr;
+  {
+    ProfScope ps(ctx, "fasta_scan_tiles", n_bytes);
+    if (carry3)
+      hipLaunchKernelGGL(fasta_scan_tiles_kernel<true>, dim3((unsigned)n_tiles), dim3(FaCfg::NT), 0, ctx->stream, bytes_dev, (uint64_t)n_bytes,
+                         first_ls, info, tcarry);
+    else
+      hipLaunchKernelGGL(fasta_scan_tiles_kernel<false>, dim3((unsigned)n_tiles), dim3(FaCfg::NT), 0, ctx->stream, bytes_dev, (uint64_t)n_bytes,
+                         first_ls, info, (uint32_t *)nullptr);
+    hipLaunchKernelGGL(fasta_offsets_reduce_kernel, dim3((unsigned)n_blocks), dim3(1024), 0, ctx->stream, (const FaTileInfo *)info, n_tiles, sums,
+                       (const uint32_t *)tcarry, gcarry);
+  }
+  KMI_HIP(ctx, hipGetLastError());
+  std::vector<FaTileSum> h(n_blocks);
+  std::vector<uint64_t> hc(carry3 ? 3 * n_blocks : 0);
+  KMI_HIP(ctx, hipMemcpyAsync(h.data(), sums, sizeof(FaTileSum) * n_blocks, hipMemcpyDeviceToHost, ctx->stream));
+  if (carry3) KMI_HIP(ctx, hipMemcpyAsync(hc.data(), gcarry, sizeof(uint64_t) * 3 * n_blocks, hipMemcpyDeviceToHost, ctx->stream));
+  KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  for (uint32_t in = 0; in < 3; ++in) {
+    uint32_t st = in; uint64_t ev = 0, last = 0;
+    for (uint64_t b = 0; b < n_blocks; ++b) {
+      if (carry3 && hc[3 * b + st]) last = hc[3 * b + st] & 0xFFFFFFFFull;   // the last group that has an event holds the range's last one
+      ev += h[b].nev[st]; st = (h[b].map >> (2u * st)) & 3u;
+    }
+    out6[2 * in] = st; out6[2 * in + 1] = ev;
+    if (carry3 && last) carry3[in] = (((last >> 8) - 1u) & 1u) ? (KMI_FA_CARRY_BYTE | (last & 0xFFu)) : (uint64_t)KMI_FA_CARRY_CUT;
+  }
+  return KMI_OK;
+}
+
+}  // namespace kmi
+
 // The line-kind machine over bytes [0, n_bytes) of a FASTA buffer in HBM, as a transfer function: for every state the machine can
 // enter the range in (KMI_FA_OUTSIDE / HEADER / SEQUENCE), the state it leaves it in and the records (header group -> sequence
 // group transitions) that start inside. What a rank tells the others about its block, so that every rank can work out where ITS
 // block starts (fasta_loader.hpp:232-456 does this with collectives over the ranks' first / last lines; file.hpp:1436-1610):
 // summaries compose left to right. out6 = {out[O], records[O], out[H], records[H], out[S], records[S]}.
 extern "C" kmi_status kmi_fasta_block_summary_dev(kmi_ctx *ctx, const uint8_t *bytes_dev, size_t n_bytes, int first_is_line_start, uint64_t *out6) {
-  using namespace kmi;
   if (!ctx || !out6) return KMI_ERR_INVALID;
-  for (uint32_t in = 0; in < 3; ++in) { out6[2 * in] = in; out6[2 * in + 1] = 0; }
-  if (n_bytes == 0) return KMI_OK;
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  const uint64_t n_tiles = (n_bytes + FaCfg::TILE - 1) / FaCfg::TILE;
-  const uint64_t n_blocks = (n_tiles + 1023) / 1024;
-  void *p;
-  KMI_TRY(ws_get(ctx, WS_TILE_INFO, sizeof(FaTileInfo) * (n_tiles + 1), &p)); FaTileInfo *info = (FaTileInfo *)p;
-  KMI_TRY(ws_get(ctx, WS_MISC, sizeof(FaTileSum) * (n_blocks + 1), &p)); FaTileSum *sums = (FaTileSum *)p;
-  {
-    ProfScope ps(ctx, "fasta_scan_tiles", n_bytes);
-    hipLaunchKernelGGL(fasta_scan_tiles_kernel, dim3((unsigned)n_tiles), dim3(FaCfg::NT), 0, ctx->stream, bytes_dev, (uint64_t)n_bytes,
-                       first_is_line_start != 0, info);
-    hipLaunchKernelGGL(fasta_offsets_reduce_kernel, dim3((unsigned)n_blocks), dim3(1024), 0, ctx->stream, (const FaTileInfo *)info, n_tiles, sums);
-  }
-  KMI_HIP(ctx, hipGetLastError());
-  std::vector<FaTileSum> h(n_blocks);
-  KMI_HIP(ctx, hipMemcpyAsync(h.data(), sums, sizeof(FaTileSum) * n_blocks, hipMemcpyDeviceToHost, ctx->stream));
-  KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  for (uint32_t in = 0; in < 3; ++in) {
-    uint32_t st = in; uint64_t ev = 0;
-    for (uint64_t b = 0; b < n_blocks; ++b) { ev += h[b].nev[st]; st = (h[b].map >> (2u * st)) & 3u; }
-    out6[2 * in] = st; out6[2 * in + 1] = ev;
-  }
-  return KMI_OK;
+  return kmi::fasta_block_summary(ctx, bytes_dev, n_bytes, first_is_line_start != 0, out6, nullptr);
 }
 
 namespace kmi {

@@ -5191,28 +5191,33 @@ kmi_status kmi_index_build_fasta_file_dist_host(kmi_index *idx, kmi_comm *comm, 
 // start before it, whether the file opens with a header -- comes from the other ranks' block summaries (kmi_fasta_block_summary_dev:
 // the line-kind machine over a block as a transfer function), gathered once and composed left to right. bytes = file bytes
 // [buffer_offset, buffer_offset + n_bytes), the first nominal_bytes of them the rank's block; prev_byte = the file byte before the
-// buffer (-1 at the file start); *need_more = 1: the k - 1 sequence characters behind the block (the last windows' overlap) do not
-// end inside the look-ahead -- nothing collective has happened, the caller reads further and calls again.
+// buffer (-1 at the file start); *need_more = 1: the `behind` sequence characters behind the block (the last windows' overlap: k - 1
+// for k-mers, k for de Bruijn tuples, whose last window also needs its right neighbour) do not end inside the look-ahead -- nothing
+// collective has happened, the caller reads further and calls again.
 // the bookkeeping of a block: *need_more (nothing collective has happened then), or the partition record and where the block's
-// windows end inside the buffer. d_bytes = the buffer on the device (already in flight on the context's stream).
-static kmi_status fasta_range_partition(kmi_ctx *ctx, kmi_comm *comm, uint32_t k, const uint8_t *bytes, const uint8_t *d_bytes, size_t n_bytes,
+// windows end inside the buffer. d_bytes = the buffer on the device (already in flight on the context's stream). carry_out
+// (optional): the raw byte of the last sequence character before the block in the same record, -1 when there is none (a record
+// starts in between, or the block opens the file) -- the in-edge of the block's first window, from the blocks' left carries
+// composed right to left.
+static kmi_status fasta_range_partition(kmi_ctx *ctx, kmi_comm *comm, uint32_t behind, const uint8_t *bytes, const uint8_t *d_bytes, size_t n_bytes,
                                         uint64_t buffer_offset, uint64_t nominal_bytes, int reaches_eof, int prev_byte, int *need_more,
-                                        kmi_fasta_partition *part_out, uint64_t *end_out) {
+                                        kmi_fasta_partition *part_out, uint64_t *end_out, int *carry_out = nullptr) {
   const uint32_t p = (uint32_t)kmi::comm_size(comm), r = (uint32_t)kmi::comm_rank(comm);
   const bool first_ls = buffer_offset == 0 || prev_byte == (int)'\n';
-  uint64_t mine[8] = {0, 0, 1, 0, 2, 0, 0, 0};
-  KMI_TRY(kmi_fasta_block_summary_dev(ctx, d_bytes, (size_t)nominal_bytes, first_ls ? 1 : 0, mine));
+  constexpr size_t NWD = 11;   // out6, the file's first byte, the block's length, the left carry per incoming state
+  uint64_t mine[NWD] = {0, 0, 1, 0, 2, 0, 0, 0, 0, 0, 0};
+  KMI_TRY(kmi::fasta_block_summary(ctx, d_bytes, (size_t)nominal_bytes, first_ls, mine, mine + 8));
   mine[6] = (buffer_offset == 0 && n_bytes) ? bytes[0] : 0;   // (rank 0: the file's first byte decides init_parser's index shift)
   mine[7] = nominal_bytes;
-  // where the overlap ends: the (k - 1)-th sequence character at or behind the block's end, for every state the machine may be in there
+  // where the overlap ends: the behind-th sequence character at or behind the block's end, for every state the machine may be in there
   auto step = [](uint32_t &state, uint8_t c) {
     if (c == '>' || c == ';') state = KMI_FA_HEADER;
     else state = (state == KMI_FA_OUTSIDE) ? (uint32_t)KMI_FA_OUTSIDE : (uint32_t)KMI_FA_SEQUENCE;
   };
   uint64_t end_for[3] = {nominal_bytes, nominal_bytes, nominal_bytes};
   for (uint32_t st0 = 0; st0 < 3; ++st0) {
-    if (k <= 1 || nominal_bytes >= n_bytes) { end_for[st0] = nominal_bytes < n_bytes ? nominal_bytes : n_bytes; continue; }
-    uint32_t st = st0, need = k - 1u;
+    if (behind == 0 || nominal_bytes >= n_bytes) { end_for[st0] = nominal_bytes < n_bytes ? nominal_bytes : n_bytes; continue; }
+    uint32_t st = st0, need = behind;
     uint64_t i = nominal_bytes;
     for (; i < n_bytes && need; ++i) {
       const uint8_t c = bytes[i];
@@ -5223,14 +5228,24 @@ static kmi_status fasta_range_partition(kmi_ctx *ctx, kmi_comm *comm, uint32_t k
     if (need && !reaches_eof) { *need_more = 1; return KMI_OK; }
     end_for[st0] = need ? n_bytes : i;
   }
-  if (k > 1 && nominal_bytes >= n_bytes && !reaches_eof && p > 1 && r + 1 < p) { *need_more = 1; return KMI_OK; }   // (no look-ahead at all behind a block that is not the file's last)
+  if (behind > 0 && nominal_bytes >= n_bytes && !reaches_eof && p > 1 && r + 1 < p) { *need_more = 1; return KMI_OK; }   // (no look-ahead at all behind a block that is not the file's last)
   // ---- collective from here on
-  std::vector<uint64_t> all((size_t)p * 8);
-  KMI_TRY(kmi::comm_allgather_words(comm, mine, 8, all.data()));
+  std::vector<uint64_t> all((size_t)p * NWD);
+  KMI_TRY(kmi::comm_allgather_words(comm, mine, NWD, all.data()));
   uint32_t st = KMI_FA_OUTSIDE; uint64_t ev = 0;
-  for (uint32_t q = 0; q < r; ++q) { const uint64_t *t = &all[(size_t)q * 8]; ev += t[2 * st + 1]; st = (uint32_t)t[2 * st]; }
+  std::vector<uint32_t> st_in(r + 1);   // the state every block before this one is entered in
+  for (uint32_t q = 0; q < r; ++q) { const uint64_t *t = &all[(size_t)q * NWD]; st_in[q] = st; ev += t[2 * st + 1]; st = (uint32_t)t[2 * st]; }
+  if (carry_out) {
+    *carry_out = -1;
+    for (uint32_t q = r; q-- > 0;) {   // the nearest block to the left that holds a sequence character or a record start decides
+      const uint64_t c = all[(size_t)q * NWD + 8 + st_in[q]];
+      if (c == kmi::KMI_FA_CARRY_PASS) continue;
+      if (c & kmi::KMI_FA_CARRY_BYTE) *carry_out = (int)(c & 0xFFu);
+      break;
+    }
+  }
   uint64_t first = 0;
-  for (uint32_t q = 0; q < p; ++q) if (all[(size_t)q * 8 + 7]) { first = all[(size_t)q * 8 + 6]; break; }   // the first non-empty block opens the file
+  for (uint32_t q = 0; q < p; ++q) if (all[(size_t)q * NWD + 7]) { first = all[(size_t)q * NWD + 6]; break; }   // the first non-empty block opens the file
   kmi_fasta_partition part; memset(&part, 0, sizeof(part));
   part.valid_bytes = nominal_bytes;
   part.start_state = buffer_offset == 0 ? (uint32_t)KMI_FA_OUTSIDE : st;
@@ -5256,8 +5271,8 @@ kmi_status kmi_index_build_fasta_range_dist_host(kmi_index *idx, kmi_comm *comm,
   KMI_TRY(ws_get(ctx, WS_INPUT, n_bytes + 64, &d_bytes));
   if (n_bytes) KMI_HIP(ctx, hipMemcpyAsync(d_bytes, bytes, n_bytes, hipMemcpyHostToDevice, ctx->stream));
   kmi_fasta_partition part; uint64_t end = 0;
-  KMI_TRY(fasta_range_partition(ctx, comm, idx->shape.k, bytes, (const uint8_t *)d_bytes, n_bytes, buffer_offset, nominal_bytes, reaches_eof, prev_byte,
-                                need_more, &part, &end));
+  KMI_TRY(fasta_range_partition(ctx, comm, idx->shape.k - 1u, bytes, (const uint8_t *)d_bytes, n_bytes, buffer_offset, nominal_bytes, reaches_eof,
+                                prev_byte, need_more, &part, &end));
   if (*need_more) return KMI_OK;
   KMI_TRY(kmi_ctx_set_fasta_partition(ctx, &part));
   const kmi_status stb = kmi_index_build_dist_dev(idx, comm, (const uint8_t *)d_bytes, (size_t)end, buffer_offset);
@@ -5280,8 +5295,8 @@ kmi_status kmi_extract_fasta_range_dist_host(kmi_ctx *ctx, const kmi_config *cfg
   KMI_TRY(ws_get(ctx, WS_INPUT2, n_bytes + 64, &d_bytes));
   if (n_bytes) KMI_HIP(ctx, hipMemcpyAsync(d_bytes, bytes, n_bytes, hipMemcpyHostToDevice, ctx->stream));
   kmi_fasta_partition part; uint64_t end = 0;
-  KMI_TRY(fasta_range_partition(ctx, comm, cfg->k, bytes, (const uint8_t *)d_bytes, n_bytes, buffer_offset, nominal_bytes, reaches_eof, prev_byte,
-                                need_more, &part, &end));
+  KMI_TRY(fasta_range_partition(ctx, comm, cfg->k - 1u, bytes, (const uint8_t *)d_bytes, n_bytes, buffer_offset, nominal_bytes, reaches_eof,
+                                prev_byte, need_more, &part, &end));
   if (*need_more || end == 0) return KMI_OK;
   KMI_TRY(kmi_ctx_set_fasta_partition(ctx, &part));
   const kmi_status st = kmi_extract_host(ctx, cfg, bytes, (size_t)end, buffer_offset, out);
@@ -5661,6 +5676,45 @@ kmi_status kmi_dbg_build_range_dist_host(kmi_dbg *g, kmi_comm *comm, const uint8
   if (cut[0] >= n_bytes && !reaches_eof && n_bytes && buffer_offset != 0) { *need_more = 1; return KMI_OK; }
   if (cut[1] < cut[0]) cut[1] = cut[0];
   return kmi_dbg_build_dist_host(g, comm, bytes + cut[0], (size_t)(cut[1] - cut[0]));
+}
+
+// build over ranks from a FASTA file by BYTE RANGE (the engine's build_posix / build_mmap<FASTAParser> with comm.size() > 1): the
+// bookkeeping of kmi_index_build_fasta_range_dist_host, where the block's windows need k sequence characters behind it (the last
+// window's right neighbour) and its first window's left neighbour comes from the blocks before it (the left carries, in the same
+// gather); then the node-form tuples of the block are routed, exchanged once and inserted as kmi_dbg_build_dist_host does
+kmi_status kmi_dbg_build_fasta_range_dist_host(kmi_dbg *g, kmi_comm *comm, const uint8_t *bytes, size_t n_bytes, uint64_t buffer_offset,
+                                               uint64_t nominal_bytes, int reaches_eof, int prev_byte, int *need_more) {
+  if (!g || !need_more) return KMI_ERR_INVALID;
+  KMI_TRY(dist_check(g->nodes, comm));
+  kmi_ctx *ctx = g->ctx;
+  *need_more = 0;
+  if (g->cfg.seq_format != KMI_FMT_FASTA) return set_err(ctx, KMI_ERR_INVALID, "not a FASTA graph (kmi_dbg_set_seq_format)");
+  if ((n_bytes && !bytes) || nominal_bytes > n_bytes) return set_err(ctx, KMI_ERR_INVALID, "bad buffer");
+  KMI_HIP(ctx, hipSetDevice(ctx->device));
+  const int p = kmi::comm_size(comm);
+  void *d_bytes;
+  KMI_TRY(ws_get(ctx, WS_INPUT, n_bytes + 64, &d_bytes));
+  if (n_bytes) KMI_HIP(ctx, hipMemcpyAsync(d_bytes, bytes, n_bytes, hipMemcpyHostToDevice, ctx->stream));
+  kmi_fasta_partition part; uint64_t end = 0; int carry = -1;
+  KMI_TRY(fasta_range_partition(ctx, comm, g->shape.k, bytes, (const uint8_t *)d_bytes, n_bytes, buffer_offset, nominal_bytes, reaches_eof,
+                                prev_byte, need_more, &part, &end, &carry));
+  if (*need_more) return KMI_OK;
+  uint64_t *recs = nullptr, nt = 0;
+  KMI_TRY(kmi_ctx_set_fasta_partition(ctx, &part));
+  ctx->fa_left_carry = carry;
+  const kmi_status stp = dbg_parse(ctx, &g->cfg, (const uint8_t *)d_bytes, (size_t)end, true, &recs, &nt);
+  ctx->fa_left_carry = -1;
+  (void)kmi_ctx_set_fasta_partition(ctx, nullptr);
+  KMI_TRY(stp);
+  if (p == 1 && !ctx->force_dist) return dbg_insert(g, recs, (size_t)nt);   // (one rank: every node is its own)
+  const uint32_t rw = g->shape.n_words + 1u;
+  void *d_send, *d_recv;
+  uint64_t total = 0;
+  KMI_TRY(ws_get(ctx, WS_DIST_A, ((size_t)nt + 64) * rw * sizeof(uint64_t), &d_send));
+  std::vector<uint64_t> sc(p, 0), rc;
+  if (nt) KMI_TRY(kmi_route_tuples_dev(ctx, &g->nodes->cfg, recs, (size_t)nt, (uint32_t)p, 1, (uint64_t *)d_send, sc.data()));
+  KMI_TRY(dist_exchange(comm, d_send, sc.data(), rw * sizeof(uint64_t), WS_DIST_B, &d_recv, rc, &total));
+  return dbg_insert(g, (const uint64_t *)d_recv, (size_t)total);
 }
 
 // erase(): the nodes of the query keys (either strand) leave the map

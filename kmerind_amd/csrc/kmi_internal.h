@@ -126,6 +126,8 @@ struct kmi_ctx {
   int sk_dbg = 0;                // KMI_SK_DBG=7 (test knob): the super-k-mer front end reports a capacity as exceeded
   bool fa_part_set = false;      // kmi_ctx_set_fasta_partition
   kmi_fasta_partition fa_part{};
+  int fa_left_carry = -1;        // de Bruijn tuples of a FASTA block (kmi_dbg_build_fasta_range_dist_host): the raw byte of the sequence
+                                 // character before the block's first one, the in-edge of its first window; -1: none
 };
 
 namespace kmi {
@@ -289,12 +291,16 @@ int comm_size(kmi_comm *c);
 int comm_rank(kmi_comm *c);
 
 // ---- entry points implemented across the .hip files
+// de Bruijn tuples from the extract pass (records of n_words + 1 words): EDGES_NODE -- the key is the smaller strand and the value word
+// 1 | edge byte << 32 (node form, what the node build inserts); EDGES_PARSED -- the k-mer as parsed and the edge byte (FASTA only:
+// de_bruijn_parser's own output)
+enum : uint32_t { EDGES_NONE = 0, EDGES_NODE = 1, EDGES_PARSED = 2 };
 kmi_status extract_count(kmi_ctx *ctx, const kmi_config *cfg, const uint8_t *bytes_dev, size_t n_bytes,
                          uint64_t *n_tuples, uint64_t *n_seqs);
 kmi_status extract_run(kmi_ctx *ctx, const kmi_config *cfg, const uint8_t *bytes_dev, size_t n_bytes,
                        uint64_t file_offset, uint64_t *out_kmers_dev, uint64_t *out_ids_dev, size_t out_capacity,
                        bool apply_strand, bool scan_done, uint64_t *n_tuples, uint64_t *n_seqs, float *out_quals_dev = nullptr,
-                       uint32_t rec_words = 0, bool edges = false);
+                       uint32_t rec_words = 0, uint32_t edges = EDGES_NONE);
 kmi_status upload_quality_lut(kmi_ctx *ctx);
 
 // tile scan of a FASTQ partition; the packed arrays and per-tile line bases stay in the workspace
@@ -326,5 +332,8 @@ struct FastaScan {
 };
 kmi_status fasta_scan(kmi_ctx *ctx, const kmi_config *cfg, const uint8_t *bytes_dev, size_t n_bytes, uint64_t file_offset, bool want_ids,
                       FastaScan *out);
+// kmi_fasta_block_summary_dev, and with carry3 the range's left carry per incoming state (a KMI_FA_CARRY_* word)
+enum : uint64_t { KMI_FA_CARRY_PASS = 0, KMI_FA_CARRY_CUT = 1, KMI_FA_CARRY_BYTE = 0x100 };
+kmi_status fasta_block_summary(kmi_ctx *ctx, const uint8_t *bytes_dev, size_t n_bytes, bool first_ls, uint64_t *out6, uint64_t *carry3);
 
 }  // namespace kmi
