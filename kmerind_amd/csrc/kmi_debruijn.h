@@ -191,7 +191,9 @@ __global__ __launch_bounds__((DbgCfg<NW>::NT)) void dbg_accumulate_kernel(const 
 // build laid out by the same minimizer buckets. One lane per record rolls through its k-mers: window -> both strands -> the smaller
 // one is the node (the edges of a node kept reverse-complemented change sides and are complemented, de_bruijn_node_trait.hpp:
 // 122-124) -> row -> two counter adds. Counters and chunks of rows as in dbg_accumulate_kernel.
-constexpr int kSkEdgeOwn = 64 * 10;   // unit marks of a wavefront's batch: 64 records of up to 9 units (18 k-mers) + slack
+// unit marks of a wavefront's batch: 64 records of up to 15 units + slack. An edge record holds sk_nmax_of(k) - kSkEdgeWindows k-mers:
+// 18 (9 units) for k = 31, but 29 (15 units) for k <= 20 -- a batch of such records (poly-A reads) wrote its marks past the wavefront's share
+constexpr int kSkEdgeOwn = 64 * 16;
 __global__ __launch_bounds__((DbgCfg<1>::NT)) void sk_edges_accumulate_kernel(const uint64_t *__restrict__ idx_keys, const uint64_t *__restrict__ idx_off,
                                                                            const uint64_t *__restrict__ recs, const uint64_t *__restrict__ rec_off,
                                                                            const uint64_t *__restrict__ fine_region, const uint32_t *__restrict__ fine_cap,
