@@ -137,6 +137,14 @@ struct de_bruijn_nodes_distributed {
 };
 
 // Index<NodeMap, de_bruijn_parser> as the engine uses it (kmer_index.hpp:100-372 of the reference)
+// one unitig of NodeIndex::unitigs(): its bases, the sum of its nodes' occurrence counts (0 for edge_exists maps), and whether it
+// is a cycle (spelled from its smallest canonical k-mer; the last k - 1 bases repeat the first)
+struct Unitig {
+  std::string sequence;
+  uint64_t occurrences = 0;
+  bool circular = false;
+};
+
 template <typename MapType, typename ParserT>
 class NodeIndex {
  public:
@@ -245,6 +253,25 @@ class NodeIndex {
       uint32_t c10[10] = {0};
       std::memcpy(c10, &c9[i * 9], 9 * sizeof(uint32_t));
       out.emplace_back(KmerType(&keys[i * KmerType::nWords]), ValueType(reinterpret_cast<const uint64_t *>(c10)));
+    }
+    return out;
+  }
+
+  // the unitigs of the map (kmi_dbg_compact: every non-branching path collapsed; the definition is in kmerind_hip.h), in unitig
+  // order. No counterpart in the reference. A map held over several ranks is refused: compaction needs the whole graph on one.
+  std::vector<Unitig> unitigs(uint32_t min_edge_count = 1) const {
+    if (comm.size() > 1) throw std::invalid_argument("unitigs() needs the whole graph on one rank (comm.size() == 1)");
+    uint64_t nu = 0, nb = 0;
+    ::kmerind::check(ctx, kmi_dbg_compact(g, min_edge_count, &nu, &nb));
+    std::vector<uint64_t> off(nu + 1), occ(nu + 1);
+    std::vector<uint8_t> circ(nu + 1);
+    std::string bases(nb, '\0');
+    ::kmerind::check(ctx, kmi_dbg_unitigs_export_host(g, off.data(), nb ? &bases[0] : nullptr, occ.data(), circ.data(), nu, nb));
+    std::vector<Unitig> out(nu);
+    for (uint64_t i = 0; i < nu; ++i) {
+      out[i].sequence = bases.substr(off[i], off[i + 1] - off[i]);
+      out[i].occurrences = occ[i];
+      out[i].circular = circ[i] != 0;
     }
     return out;
   }

@@ -543,6 +543,34 @@ kmi_status kmi_dbg_erase_dist_host(kmi_dbg *g, kmi_comm *comm, const uint64_t *q
 kmi_status kmi_dbg_count_dist_host(kmi_dbg *g, kmi_comm *comm, const uint64_t *queries, size_t nq, kmi_results *out); /* count(): collective */
 kmi_status kmi_dbg_size_dist(kmi_dbg *g, kmi_comm *comm, uint64_t *n);                                /* size() */
 
+/* ---- unitigs of a node map (no counterpart in the reference: its test/test/debruijn/ ends at the node map)
+ * Compaction collapses every non-branching path of the graph below into one unitig. With t = min_edge_count >= 1:
+ *  1. Degree of an end. A node v has an out end and an in end, in its stored (lexicographically smaller) orientation. The degree
+ *     of an end is the number of bases whose counter at that end is >= t. Only v's own counters count, so an edge to a k-mer that
+ *     is not a node (a DNA16 'N' neighbour, a node erased) still counts toward the degree. EDGE_EXISTS counters are 0 / 1.
+ *  2. Links. The out end of v, with its single base b, links to the node w = canonical(v[1..k-1] + b) only if w is a node; w != v
+ *     (self-loops and hairpins v -> rc(v) never link); the end of w that is entered has degree 1; and its counter for the
+ *     reciprocal base is >= t: the in end and base v[0] if w is stored forward, the out end and base comp(v[0]) if w is stored
+ *     reverse-complemented. The in end of v works the same way, with w = canonical(c + v[0..k-2]).
+ *  3. Palindromes. A node whose k-mer equals its reverse complement (even k only) links to nothing.
+ *  4. Components. Links are symmetric and each end has at most one, so the linked components are simple paths and simple cycles.
+ *     Each one is a unitig; every node is in exactly one.
+ *  5. Spelling. A path of L nodes is its L + k - 1 bases in whichever direction gives the lexicographically smaller string (the
+ *     direction whose first oriented k-mer is smaller). A cycle of L nodes is spelled from its node with the smallest canonical
+ *     k-mer, in that node's stored orientation, as L + k - 1 bases (the last k - 1 repeat the first), and flagged circular. The
+ *     letters are the alphabet's (ACGT; ACGU for RNA).
+ *  6. Occurrences. Per unitig, the sum of counts[8] over its nodes (0 for an EDGE_EXISTS map).
+ * Unitigs are numbered in the order of the entries of their first nodes. Only 2-bit alphabets (DNA, RNA) are supported, for every
+ * k the node map takes; anything else, t = 0, or a map that holds one rank's share of a build over more than one rank
+ * (kmi_dbg_build_dist_host / *_range_dist_host with comm size > 1, until kmi_dbg_clear) gives KMI_ERR_INVALID.
+ * kmi_dbg_compact runs on the device and keeps the result in the graph; every build, insert, erase or clear drops it. */
+kmi_status kmi_dbg_compact(kmi_dbg *g, uint32_t min_edge_count, uint64_t *n_unitigs, uint64_t *n_bases);
+/* the result of the last kmi_dbg_compact: offsets[n_unitigs + 1] (unitig i is bases[offsets[i], offsets[i + 1])), bases (not
+ * NUL-terminated), occurrences[n_unitigs], circular[n_unitigs] (0 / 1). Any output may be NULL. KMI_ERR_INVALID when the map has
+ * not been compacted since it last changed; KMI_ERR_OVERFLOW when a capacity is too small. */
+kmi_status kmi_dbg_unitigs_export_host(kmi_dbg *g, uint64_t *offsets, char *bases, uint64_t *occurrences, uint8_t *circular,
+                                       size_t capacity_unitigs, size_t capacity_bases);
+
 /* ---- measurement support --------------------------------------------------- */
 /* per-kernel HIP-event timing on the context's stream (bench.py roofline leg) */
 kmi_status kmi_profile_enable(kmi_ctx *ctx, int on);

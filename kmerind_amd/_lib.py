@@ -173,6 +173,8 @@ SIGNATURES = {
     "kmi_dbg_erase_dist_host": (C.c_int, [_P, _P, _P, _sz, C.POINTER(_u64)]),
     "kmi_dbg_count_dist_host": (C.c_int, [_P, _P, _P, _sz, C.POINTER(Results)]),
     "kmi_dbg_size_dist": (C.c_int, [_P, _P, C.POINTER(_u64)]),
+    "kmi_dbg_compact": (C.c_int, [_P, _u32, C.POINTER(_u64), C.POINTER(_u64)]),
+    "kmi_dbg_unitigs_export_host": (C.c_int, [_P, _P, _P, _P, _P, _sz, _sz]),
     "kmi_profile_enable": (C.c_int, [_P, C.c_int]),
     "kmi_profile_reset": (C.c_int, [_P]),
     "kmi_profile_get": (C.c_int, [_P, C.POINTER(KernelTime), _sz, C.POINTER(_sz)]),

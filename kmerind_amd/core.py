@@ -466,6 +466,31 @@ class DeBruijnNodes:
         lib.kmi_results_free(C.byref(r))
         return keys, vals
 
+    def unitigs(self, min_edge_count=1):
+        """Compacts the map on the device (kmi_dbg_compact; the definition is in include/kmerind_hip.h) ->
+        (offsets: uint64[n + 1], bases: uint8[offsets[-1]] (ASCII letters), occurrences: uint64[n], circular: bool[n]).
+        Unitig i is bases[offsets[i]:offsets[i + 1]]."""
+        nu, nb = C.c_uint64(), C.c_uint64()
+        self.ctx.check(lib.kmi_dbg_compact(self.h, int(min_edge_count), C.byref(nu), C.byref(nb)))
+        offsets = np.zeros(nu.value + 1, dtype=np.uint64)
+        bases = np.zeros(max(nb.value, 1), dtype=np.uint8)
+        occ = np.zeros(max(nu.value, 1), dtype=np.uint64)
+        circ = np.zeros(max(nu.value, 1), dtype=np.uint8)
+        self.ctx.check(lib.kmi_dbg_unitigs_export_host(self.h, offsets.ctypes.data_as(C.c_void_p), bases.ctypes.data_as(C.c_void_p),
+                                                       occ.ctypes.data_as(C.c_void_p), circ.ctypes.data_as(C.c_void_p),
+                                                       nu.value, nb.value))
+        return offsets, bases[:nb.value], occ[:nu.value], circ[:nu.value].astype(bool)
+
+    def unitig_sequences(self, min_edge_count=1):
+        """the sequences of unitigs() as a list of bytes, in unitig order"""
+        return split_unitigs(*self.unitigs(min_edge_count)[:2])
+
+
+def split_unitigs(offsets, bases):
+    """(offsets, bases) of DeBruijnNodes.unitigs() -> list of bytes"""
+    raw = np.ascontiguousarray(bases, dtype=np.uint8).tobytes()
+    return [raw[int(offsets[i]):int(offsets[i + 1])] for i in range(len(offsets) - 1)]
+
 
 def synth_fastq(seed, genome_len, n_reads, read_len=150, first_read=0, threads=None):
     """SURVEY.md 8(d) synthetic FASTQ as a numpy uint8 array (host)."""

@@ -372,6 +372,14 @@ struct kmi_dbg {
   kmi_index *nodes = nullptr;   // canonical k-mer -> occurrences (a count index, laid out by the placement hash)
   uint32_t *edges = nullptr;    // [n_entries][8]: out A C G T, in A C G T, in the order of nodes->keys
   size_t edges_bytes = 0;
+  bool dist_share = false;      // a build over more than one rank ran: the map holds this rank's share (kmi_dbg_compact refuses it)
+  // the unitigs of the last kmi_dbg_compact (kmi_unitig.h), until the map changes: one block of offsets[n + 1], occurrences[n],
+  // circular[n] (padded to 16 bytes), bases
+  bool uni_valid = false;
+  void *uni_buf = nullptr;
+  size_t uni_bytes = 0;
+  uint64_t n_unitigs = 0, n_unitig_bases = 0;
+  uint32_t unitig_rounds = 0;   // pointer-jumping rounds of the last compaction
 };
 
 namespace kmi {

@@ -4334,6 +4334,7 @@ static kmi_status sk_consume(kmi_index *idx, uint32_t w, const uint64_t *recs_de
 static bool sk_rank_count(uint32_t p) { return p == 1u || p == 2u || p == 4u || p == 8u; }
 
 #include "kmi_debruijn.h"
+#include "kmi_unitig.h"
 #include "kmi_update.h"
 
 struct kmi_comm;
@@ -5428,6 +5429,7 @@ kmi_status kmi_dbg_destroy(kmi_dbg *g) {
   if (!g) return KMI_OK;
   (void)hipSetDevice(g->ctx->device);
   (void)hipStreamSynchronize(g->ctx->stream);
+  dbg_unitigs_drop(g);
   if (g->edges) pool_free(g->ctx, g->edges, g->edges_bytes);
   (void)kmi_index_destroy(g->nodes);
   delete g;
@@ -5437,8 +5439,10 @@ kmi_status kmi_dbg_destroy(kmi_dbg *g) {
 kmi_status kmi_dbg_clear(kmi_dbg *g) {
   if (!g) return KMI_ERR_INVALID;
   KMI_TRY(kmi_index_clear(g->nodes));
+  dbg_unitigs_drop(g);
   if (g->edges) pool_free(g->ctx, g->edges, g->edges_bytes);
   g->edges = nullptr; g->edges_bytes = 0;
+  g->dist_share = false;
   return KMI_OK;
 }
 
@@ -5468,6 +5472,7 @@ kmi_status kmi_dbg_build_dev(kmi_dbg *g, const uint8_t *bytes_dev, size_t n_byte
   kmi_ctx *ctx = g->ctx;
   KMI_HIP(ctx, hipSetDevice(ctx->device));
   if (n_bytes == 0) return KMI_OK;
+  dbg_unitigs_drop(g);
   {   // an empty graph from clean FASTQ reads: through super-k-mer records (dbg_build_superkmer); else, and for what that declines, tuples
     bool done = false;
     KMI_TRY(dbg_build_superkmer(g, bytes_dev, n_bytes, &done));
@@ -5492,6 +5497,7 @@ kmi_status kmi_dbg_build_host(kmi_dbg *g, const uint8_t *bytes, size_t n_bytes) 
 
 // tuples as the parser emits them (any strand; value word = edge byte); they are rewritten in place into node form
 static kmi_status dbg_insert_tuples(kmi_dbg *g, uint64_t *recs_dev, size_t n) {
+  dbg_unitigs_drop(g);
   KMI_TRY(dbg_edges(g->ctx, recs_dev, n, nullptr, 0, g->shape, false, true));
   return dbg_insert(g, recs_dev, n);
 }
@@ -5603,6 +5609,8 @@ kmi_status kmi_dbg_build_dist_host(kmi_dbg *g, kmi_comm *comm, const uint8_t *by
   std::vector<uint64_t> sc(p, 0), rc;
   if (nt) KMI_TRY(kmi_route_tuples_dev(ctx, &g->nodes->cfg, recs, (size_t)nt, (uint32_t)p, 1, (uint64_t *)d_send, sc.data()));
   KMI_TRY(dist_exchange(comm, d_send, sc.data(), rw * sizeof(uint64_t), WS_DIST_B, &d_recv, rc, &total));
+  dbg_unitigs_drop(g);
+  if (p > 1) g->dist_share = true;
   return dbg_insert(g, (const uint64_t *)d_recv, (size_t)total);
 }
 
@@ -5706,6 +5714,7 @@ kmi_status kmi_dbg_build_fasta_range_dist_host(kmi_dbg *g, kmi_comm *comm, const
   ctx->fa_left_carry = -1;
   (void)kmi_ctx_set_fasta_partition(ctx, nullptr);
   KMI_TRY(stp);
+  dbg_unitigs_drop(g);
   if (p == 1 && !ctx->force_dist) return dbg_insert(g, recs, (size_t)nt);   // (one rank: every node is its own)
   const uint32_t rw = g->shape.n_words + 1u;
   void *d_send, *d_recv;
@@ -5714,6 +5723,8 @@ kmi_status kmi_dbg_build_fasta_range_dist_host(kmi_dbg *g, kmi_comm *comm, const
   std::vector<uint64_t> sc(p, 0), rc;
   if (nt) KMI_TRY(kmi_route_tuples_dev(ctx, &g->nodes->cfg, recs, (size_t)nt, (uint32_t)p, 1, (uint64_t *)d_send, sc.data()));
   KMI_TRY(dist_exchange(comm, d_send, sc.data(), rw * sizeof(uint64_t), WS_DIST_B, &d_recv, rc, &total));
+  dbg_unitigs_drop(g);
+  if (p > 1) g->dist_share = true;
   return dbg_insert(g, (const uint64_t *)d_recv, (size_t)total);
 }
 
@@ -5728,6 +5739,7 @@ kmi_status kmi_dbg_erase_host(kmi_dbg *g, const uint64_t *queries, size_t nq, ui
   void *dq;
   KMI_TRY(ws_get(ctx, WS_INPUT, (nq + 8) * g->shape.n_words * sizeof(uint64_t), &dq));
   KMI_HIP(ctx, hipMemcpyAsync(dq, queries, nq * g->shape.n_words * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+  dbg_unitigs_drop(g);
   return dbg_erase(g, (const uint64_t *)dq, nq, n_erased);
 }
 
@@ -5749,6 +5761,7 @@ kmi_status kmi_dbg_erase_dist_host(kmi_dbg *g, kmi_comm *comm, const uint64_t *q
   KMI_TRY(kmi_route_dev(ctx, &g->nodes->cfg, (const uint64_t *)d_in, nq, (uint32_t)p, (uint64_t *)d_send, sc.data()));
   uint64_t total = 0;
   KMI_TRY(dist_exchange(comm, d_send, sc.data(), kb, WS_DIST_B, &d_q, rc, &total));
+  dbg_unitigs_drop(g);
   return dbg_erase(g, (const uint64_t *)d_q, (size_t)total, n_erased_local);
 }
 
@@ -5761,6 +5774,43 @@ kmi_status kmi_dbg_count_dist_host(kmi_dbg *g, kmi_comm *comm, const uint64_t *q
 kmi_status kmi_dbg_size_dist(kmi_dbg *g, kmi_comm *comm, uint64_t *n) {
   if (!g) return KMI_ERR_INVALID;
   return kmi_index_size_dist(g->nodes, comm, n);
+}
+
+// unitigs (kmi_unitig.h): compaction on the device, the result kept in the graph until it changes
+kmi_status kmi_dbg_compact(kmi_dbg *g, uint32_t min_edge_count, uint64_t *n_unitigs, uint64_t *n_bases) {
+  if (!g) return KMI_ERR_INVALID;
+  kmi_ctx *ctx = g->ctx;
+  if (n_unitigs) *n_unitigs = 0;
+  if (n_bases) *n_bases = 0;
+  KMI_HIP(ctx, hipSetDevice(ctx->device));
+  KMI_TRY(dbg_compact(g, min_edge_count));
+  if (n_unitigs) *n_unitigs = g->n_unitigs;
+  if (n_bases) *n_bases = g->n_unitig_bases;
+  return KMI_OK;
+}
+
+kmi_status kmi_dbg_unitigs_export_host(kmi_dbg *g, uint64_t *offsets, char *bases, uint64_t *occurrences, uint8_t *circular,
+                                       size_t capacity_unitigs, size_t capacity_bases) {
+  if (!g) return KMI_ERR_INVALID;
+  kmi_ctx *ctx = g->ctx;
+  if (!g->uni_valid) return set_err(ctx, KMI_ERR_INVALID, "no unitigs: kmi_dbg_compact has not run since the map last changed");
+  const uint64_t nu = g->n_unitigs, nb = g->n_unitig_bases;
+  if ((offsets || occurrences || circular) && capacity_unitigs < nu) return set_err(ctx, KMI_ERR_OVERFLOW, "unitigs export: capacity_unitigs too small");
+  if (bases && capacity_bases < nb) return set_err(ctx, KMI_ERR_OVERFLOW, "unitigs export: capacity_bases too small");
+  if (nu == 0) {
+    if (offsets) offsets[0] = 0;
+    return KMI_OK;
+  }
+  KMI_HIP(ctx, hipSetDevice(ctx->device));
+  const uint64_t *u_off = (const uint64_t *)g->uni_buf, *u_occ = u_off + nu + 1u;
+  const uint8_t *u_circ = (const uint8_t *)(u_occ + nu);
+  const char *u_bases = (const char *)(u_circ + (((size_t)nu + 15u) & ~(size_t)15u));
+  if (offsets) KMI_HIP(ctx, hipMemcpyAsync(offsets, u_off, (size_t)(nu + 1u) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (occurrences) KMI_HIP(ctx, hipMemcpyAsync(occurrences, u_occ, (size_t)nu * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (circular) KMI_HIP(ctx, hipMemcpyAsync(circular, u_circ, (size_t)nu, hipMemcpyDeviceToHost, ctx->stream));
+  if (bases && nb) KMI_HIP(ctx, hipMemcpyAsync(bases, u_bases, (size_t)nb, hipMemcpyDeviceToHost, ctx->stream));
+  KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return KMI_OK;
 }
 
 // ---- builds over ranks through exchanged super-k-mer records

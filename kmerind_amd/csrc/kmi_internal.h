@@ -56,6 +56,10 @@ enum WsSlot {
   WS_DBG_POS,         // ... entry positions of the nodes a find() hit
   WS_REDO,            // sk_reduce2's redo list: buckets that go through sk_reduce behind it
   WS_ALIGNED,         // 16-byte aligned copy of an input buffer that arrived at an odd address (a batch inside a larger buffer)
+  WS_UNI_TAB,         // unitig compaction (kmi_unitig.h): entry-position table of the neighbour lookups
+  WS_UNI_NEXT,        // ... next state of every (node, direction)
+  WS_UNI_RANK,        // ... ranking records, two halves (ping-pong; the idle half holds the cycle pass and the scan)
+  WS_UNI_NODE,        // ... device scalars, per-node direction and circular flags
   WS_NUM_SLOTS
 };
 

@@ -3,7 +3,10 @@ and the checker's CPU restatement on a bounded sample for scale.
   python tools/dbg_bench.py [reads] [genome] [k]
 FASTA: a synthetic genome of 60-character lines (8 records), built from host bytes on one rank -- kmi_dbg_build_host over the whole
 file, and kmi_dbg_build_fasta_range_dist_host over a one-rank communicator on the same bytes -- with per-kernel times.
-  python tools/dbg_bench.py --fasta [genome] [k]"""
+  python tools/dbg_bench.py --fasta [genome] [k]
+Unitigs: the node map of the FASTQ input above (default: config 2's, 10 M reads of a 100 Mbp genome, k = 31), then kmi_dbg_compact
+timed warm, with its pointer-jumping rounds, per-kernel times and unitig statistics.
+  python tools/dbg_bench.py --unitigs [reads] [genome] [k]"""
 import ctypes as C
 import os
 import sys
@@ -81,9 +84,44 @@ def main_fasta(argv):
     L.lib.kmi_comm_destroy(comm)
 
 
+def main_unitigs(argv):
+    from kmerind_amd import _lib as L
+    n_reads = int(argv[0]) if len(argv) > 0 else 10_000_000
+    genome = int(argv[1]) if len(argv) > 1 else 100_000_000
+    k = int(argv[2]) if len(argv) > 2 else 31
+    host = np.asarray(K.synth_fastq(seed=2, genome_len=genome, n_reads=n_reads))   # (config 2's seed)
+    dev = torch.device("cuda", 0)
+    d = torch.from_numpy(host).to(dev)
+    ctx = K.Context(0, stream=torch.cuda.current_stream(dev).cuda_stream)
+    g = K.DeBruijnNodes(ctx, K.make_config(k))
+    g.build_device(d.data_ptr(), host.size)
+    del d
+    torch.cuda.synchronize()
+    nu, nb = C.c_uint64(), C.c_uint64()
+
+    def compact():
+        ctx.check(L.lib.kmi_dbg_compact(g.h, 1, C.byref(nu), C.byref(nb)))
+    steps = 5
+    dt, prof = timed(ctx, steps, compact)
+    ctx.profile(True); ctx.profile_reset()
+    compact()
+    rounds = sum(p["launches"] for p in ctx.profile_get() if p["name"] == "unitig_jump")
+    ctx.profile(False)
+    off, bases, occ, circ = g.unitigs(1)
+    lens = np.sort(np.diff(off.astype(np.int64)))[::-1]
+    n50 = int(lens[np.searchsorted(np.cumsum(lens), lens.sum() / 2)]) if lens.size else 0
+    print("unitigs of the de Bruijn graph, k=%d, %d reads over %d bp, %d nodes: kmi_dbg_compact %.2f ms (warm, mean of %d), %d jumping rounds"
+          % (k, n_reads, genome, g.local_size(), dt * 1e3, steps, rounds))
+    print(prof)
+    print("%d unitigs, %d bases, %d circular; length max %d, mean %.1f, N50 %d; occurrences %d"
+          % (nu.value, nb.value, int(circ.sum()), int(lens[0]) if lens.size else 0, float(lens.mean()) if lens.size else 0.0, n50, int(occ.sum())))
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--fasta":
         return main_fasta(sys.argv[2:])
+    if len(sys.argv) > 1 and sys.argv[1] == "--unitigs":
+        return main_unitigs(sys.argv[2:])
     n_reads = int(sys.argv[1]) if len(sys.argv) > 1 else 2_000_000
     genome = int(sys.argv[2]) if len(sys.argv) > 2 else 20_000_000
     k = int(sys.argv[3]) if len(sys.argv) > 3 else 31
