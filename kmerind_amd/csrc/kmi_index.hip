@@ -5110,6 +5110,7 @@ kmi_status kmi_index_build_dist_dev(kmi_index *idx, kmi_comm *comm, const uint8_
         default: return build_dist_superkmer<7>(idx, comm, d_bytes, n_bytes, file_offset);
       }
     }
+    KMI_TRY(align_input(ctx, &d_bytes, n_bytes));   // (the scan's 16-byte loads: a range build hands in its buffer + the first record's offset)
     if (n_bytes) KMI_TRY(extract_count(ctx, &idx->cfg, d_bytes, n_bytes, &nt, &ns));   // (an empty share still enters the collectives)
     KMI_TRY(ws_get(ctx, WS_DIST_A, (nt + 64) * nw * sizeof(uint64_t), &d_send));
     if (by_owner) {
@@ -5132,6 +5133,7 @@ kmi_status kmi_index_build_dist_dev(kmi_index *idx, kmi_comm *comm, const uint8_
     KMI_TRY(dist_exchange(comm, d_send, sc.data(), nw * sizeof(uint64_t), WS_DIST_B, &d_recv, rc, &total));
     return index_insert(idx, (const uint64_t *)d_recv, (size_t)total, false);
   }
+  KMI_TRY(align_input(ctx, &d_bytes, n_bytes));
   if (n_bytes) KMI_TRY(extract_count(ctx, &idx->cfg, d_bytes, n_bytes, &nt, &ns));
   if (vw == 2 && idx->cfg.seq_format != KMI_FMT_FASTQ)
     return set_err(ctx, KMI_ERR_INVALID, "a position + quality index over ranks is built from FASTQ partitions");
