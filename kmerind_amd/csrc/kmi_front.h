@@ -393,19 +393,57 @@ __global__ __launch_bounds__(kFrThreads) void sk_front_kernel(const uint8_t *__r
       }
       FQ_MARK(4)
       if (__any(cnt >= (uint32_t)CAP)) { why |= 128u; bail = true; break; }
+      // behind the last entry: one that lies behind every run (window 127), so an entry's successor is read without asking whether
+      // there is one (cnt < CAP: the value is 127; made from cnt, it is not a constant that occupies a register through the walk)
+      list[cnt * kWave + lane] = cnt | 127u;
       wave_sync();
       // items in their final form ((n - 1) | 27 hash bits << 5: the 18 bucket bits and nine more below them; the items of a run cover
       // its windows without a gap, so an item's first window is the sum of the lengths before it) + the coarse counts.
-      // Backwards, written from the top of the list down: a super-k-mer longer than nmax windows (one minimizer repeated: low
-      // complexity) becomes several items, and what is written must not reach what has not been read yet.
-      uint32_t top = (uint32_t)CAP + 2u;   // items end up in slots top .. CAP + 1
+      // FORWARD, in place, as long as no lane of the wavefront holds a super-k-mer longer than nmax windows: the entries of a lane that
+      // lie inside its run are a prefix of its list (windows ascend), entry j's length is the next entry's window (or L) minus its
+      // own, and item j goes where entry j was -- straight-line code, one entry per turn, the next two read ahead. The wavefront
+      // leaves this loop at the first turn j* in which some lane would need more than one item; items 0 .. j* - 1 are final then
+      // (and counted), and the loop below works the entries from j* on.
+      const uint32_t cmax = (uint32_t)__builtin_amdgcn_readlane((int)wave_inclusive_max_dpp(cnt), kWave - 1);
+      uint32_t jstar = cmax, head = 0;   // head: this lane's items in slots 0 .. head - 1
       {
+        // entry J (in CUR) and the one behind it (in NX); leaves the loop when a lane needs more than one item, or when no lane has an
+        // entry left. (A macro with its own `break`s: as a lambda that answers "go on" the two uniform exits came out as exec-mask
+        // control flow, and a constant marker value or two copy-out loops below cost the kernel two to three registers in the walk.)
+#define KMI_FR_TURN(J, CUR, NX)                                                                   \
+        {                                                                                         \
+          const uint32_t w0 = (CUR) & 127u, wn = (NX) & 127u;                                     \
+          const bool valid = (J) < cnt && w0 < L;                                                 \
+          const uint32_t n = (wn < L ? wn : L) - w0; /* (the entry behind a lane's last one has window 127) */ \
+          if (__any(valid && n > nmax)) { jstar = (J); break; }                                   \
+          if (!__any(valid)) break;                                                               \
+          if (valid) {                                                                            \
+            const uint32_t h27 = sk_bucket_bits27((CUR) >> 7);                                    \
+            atomicAdd(&hist[h27 >> 19], 1u);                                                      \
+            list[(J) * kWave + lane] = (n - 1u) | (h27 << 5);                                     \
+            ++head;                                                                               \
+          }                                                                                       \
+        }
+        // two turns per trip: the two entries behind them are read first (one LDS instruction) and are not needed before the trip's end
+        uint32_t e0 = list[lane], e1 = list[kWave + lane];
+        for (uint32_t j = 0; j < cmax; j += 2u) {
+          const uint32_t e2 = list[(j + 2u) * kWave + lane], e3 = list[(j + 3u) * kWave + lane];   // (slots up to cmax + 2 <= CAP + 1)
+          KMI_FR_TURN(j, e0, e1)
+          KMI_FR_TURN(j + 1u, e1, e2)
+          e0 = e2; e1 = e3;
+        }
+#undef KMI_FR_TURN
+      }
+      // The rest (low complexity: one minimizer repeated), entries jstar .. cmax - 1: backwards, written from the top of the list
+      // down -- a super-k-mer longer than nmax windows becomes several items, and what is written must not reach what has not been
+      // read yet.
+      uint32_t top = (uint32_t)CAP + 2u;   // these items end up in slots top .. CAP + 1
+      if (jstar < cmax) {
         uint32_t nxt_w = L;
-        const uint32_t cmax = (uint32_t)__builtin_amdgcn_readlane((int)wave_inclusive_max_dpp(cnt), kWave - 1);
-        uint32_t it_nx = cmax ? list[(cmax - 1u) * kWave + lane] : 0u;   // (read one turn ahead; a turn writes above the entry it works on)
-        for (uint32_t jj = cmax; jj-- > 0u;) {
+        uint32_t it_nx = list[(cmax - 1u) * kWave + lane];   // (read one turn ahead; a turn writes above the entry it works on)
+        for (uint32_t jj = cmax; jj-- > jstar;) {
           const uint32_t it = it_nx;
-          if (jj) it_nx = list[(jj - 1u) * kWave + lane];
+          if (jj > jstar) it_nx = list[(jj - 1u) * kWave + lane];
           const uint32_t w0 = it & 127u;
           if (jj < cnt && w0 < L) {
             const uint32_t h27 = sk_bucket_bits27(it >> 7);
@@ -424,8 +462,9 @@ __global__ __launch_bounds__(kFrThreads) void sk_front_kernel(const uint8_t *__r
           }
         }
       }
-      if (__any(top == 0xffffffffu)) { why |= 128u; bail = true; break; }
-      cnt = cnt ? (uint32_t)CAP + 2u - top : 0u;
+      const uint32_t tail = (uint32_t)CAP + 2u - top;   // (no room: top = 0xffffffff makes it CAP + 3)
+      if (__any(head + tail > (uint32_t)CAP)) { why |= 128u; bail = true; break; }   // more than CAP items in a run
+      cnt = head + tail;
       FQ_MARK(5)
       const uint32_t cinc = wave_inclusive_sum_dpp(cnt);
       const uint32_t ctot = __builtin_amdgcn_readlane(cinc, kWave - 1);
@@ -433,7 +472,8 @@ __global__ __launch_bounds__(kFrThreads) void sk_front_kernel(const uint8_t *__r
       if (mine) {
         const uint32_t ex = item_count + cinc - cnt;
         uint32_t *dst = items + (uint64_t)r * item_cap + ex;
-        for (uint32_t j = 0; j < cnt; ++j) dst[j] = list[(top + j) * kWave + lane];
+        if (jstar == cmax) for (uint32_t j = 0; j < cnt; ++j) dst[j] = list[j * kWave + lane];   // (uniform)
+        else for (uint32_t j = 0; j < cnt; ++j) dst[j] = list[(j < head ? j : top + j - head) * kWave + lane];   // the two segments, in window order
         const uint64_t ri = (uint64_t)r * run_cap + run_count + lane;
         run_items[ri] = ex | (cnt << 26);
       }
