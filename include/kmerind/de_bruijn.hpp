@@ -258,11 +258,16 @@ class NodeIndex {
   }
 
   // the unitigs of the map (kmi_dbg_compact: every non-branching path collapsed; the definition is in kmerind_hip.h), in unitig
-  // order. No counterpart in the reference. A map held over several ranks is refused: compaction needs the whole graph on one.
+  // order. No counterpart in the reference. With comm.size() > 1 (RCCL id or transport; or one rank under KMI_FORCE_DIST=1) the call is collective
+  // (kmi_dbg_compact_dist_host): the graph is the union of the ranks' maps and the result is the unitigs THIS rank holds, each unitig
+  // on the rank of its first node; unitigs_total() then gives the counts over all ranks.
   std::vector<Unitig> unitigs(uint32_t min_edge_count = 1) const {
-    if (comm.size() > 1) throw std::invalid_argument("unitigs() needs the whole graph on one rank (comm.size() == 1)");
     uint64_t nu = 0, nb = 0;
-    ::kmerind::check(ctx, kmi_dbg_compact(g, min_edge_count, &nu, &nb));
+    if (rccl) ::kmerind::check(ctx, kmi_dbg_compact_dist_host(g, rccl, min_edge_count, &nu, &nb, &total_unitigs, &total_bases));   // collective
+    else {
+      ::kmerind::check(ctx, kmi_dbg_compact(g, min_edge_count, &nu, &nb));
+      total_unitigs = nu; total_bases = nb;
+    }
     std::vector<uint64_t> off(nu + 1), occ(nu + 1);
     std::vector<uint8_t> circ(nu + 1);
     std::string bases(nb, '\0');
@@ -275,6 +280,9 @@ class NodeIndex {
     }
     return out;
   }
+
+  // (unitigs, bases) over all ranks of the last unitigs() call
+  std::pair<uint64_t, uint64_t> unitigs_total() const { return std::make_pair(total_unitigs, total_bases); }
 
   kmi_ctx *context() const { return ctx; }
 
@@ -313,6 +321,7 @@ class NodeIndex {
   kmi_ctx *ctx = nullptr;
   kmi_dbg *g = nullptr;
   kmi_comm *rccl = nullptr;
+  mutable uint64_t total_unitigs = 0, total_bases = 0;
 };
 
 // de_bruijn_construct_engine.hpp:241-242

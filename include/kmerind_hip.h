@@ -97,7 +97,8 @@ kmi_status kmi_ctx_destroy(kmi_ctx *ctx);
 kmi_status kmi_ctx_reset_hints(kmi_ctx *ctx);
 /* counters the library keeps for its tests and for diagnosis (no reference counterpart). which = 0: times a build over ranks had to
  * enlarge its receive pool (kmi_index_build_dist_dev); 1: microseconds this context has spent inside hipMalloc / hipFree; 2: bytes
- * and 3: calls that reached hipMalloc; 4: blocks taken from the process-wide cache instead */
+ * and 3: calls that reached hipMalloc; 4: blocks taken from the process-wide cache instead; 5: pointer-jumping rounds, 6: exchanges
+ * and 7: bytes this rank sent in the context's last kmi_dbg_compact_dist_host */
 kmi_status kmi_ctx_debug_counter(const kmi_ctx *ctx, uint32_t which, uint64_t *value);
 /* A destroyed context leaves its large device blocks (workspace, spare index arrays: >= 1 MB each, 96 GB / 64 blocks at most) in a
  * process-wide cache per device, where the next context of that device finds them: its first build then does not wait for
@@ -565,7 +566,28 @@ kmi_status kmi_dbg_size_dist(kmi_dbg *g, kmi_comm *comm, uint64_t *n);          
  * (kmi_dbg_build_dist_host / *_range_dist_host with comm size > 1, until kmi_dbg_clear) gives KMI_ERR_INVALID.
  * kmi_dbg_compact runs on the device and keeps the result in the graph; every build, insert, erase or clear drops it. */
 kmi_status kmi_dbg_compact(kmi_dbg *g, uint32_t min_edge_count, uint64_t *n_unitigs, uint64_t *n_bases);
-/* the result of the last kmi_dbg_compact: offsets[n_unitigs + 1] (unitig i is bases[offsets[i], offsets[i + 1])), bases (not
+/* ... of a map held over the ranks of a communicator (collective). The graph is the union of the ranks' node maps: what a
+ * collective build left behind, possibly changed since by kmi_dbg_erase_dist_host / kmi_dbg_insert_*; rules 1-6 above apply to that
+ * union unchanged. In addition:
+ *  - Ownership. Each unitig is held by exactly one rank: the one whose map holds its first node in spelling order (a path: the node
+ *    whose oriented k-mer starts the spelled string; a cycle: its node with the smallest canonical k-mer).
+ *  - Order. A rank's unitigs are numbered in the order of the entries of those first nodes in its node map, as above.
+ *  - Result. Kept in the graph, read with kmi_dbg_unitigs_export_host (this rank's unitigs), dropped by every build, insert, erase
+ *    or clear. *_local: this rank's unitigs and bases; *_total: the sums over the ranks, the same on every rank. Any output may
+ *    be NULL.
+ *  - One rank. A one-rank communicator gives what kmi_dbg_compact gives (with KMI_FORCE_DIST=1 through the code of several ranks,
+ *    the rank being its own peer).
+ * KMI_ERR_INVALID: not a 2-bit alphabet, t = 0, a communicator of another context, more than 256 ranks (the limit of the library's
+ * routing). KMI_ERR_OVERFLOW: 2^31 - 1 or more nodes on this rank; a global state is rank << 32 | 2 * node + direction, which has
+ * room for 2^16 ranks, and distances and occurrence sums are 64-bit, so they do not wrap for any graph that fits. A rank that fails
+ * on its own (these, or KMI_ERR_NOMEM for the workspace of its own nodes or for its result) does not leave its peers waiting: the
+ * verdict is agreed on by an all-reduce before the first exchange and again before the last, and the peers return KMI_ERR_PEER.
+ * (Receive buffers, whose size depends on what the peers send, grow inside an exchange as in the library's other collectives.) The number of pointer-jumping rounds is decided over all ranks (at most
+ * ceil(log2(states of all ranks)) + 1); kmi_ctx_debug_counter 5..7 give the rounds, exchanges and bytes sent by this rank for the
+ * last call. */
+kmi_status kmi_dbg_compact_dist_host(kmi_dbg *g, kmi_comm *comm, uint32_t min_edge_count, uint64_t *n_unitigs_local, uint64_t *n_bases_local,
+                                     uint64_t *n_unitigs_total, uint64_t *n_bases_total);
+/* the result of the last kmi_dbg_compact / kmi_dbg_compact_dist_host: offsets[n_unitigs + 1] (unitig i is bases[offsets[i], offsets[i + 1])), bases (not
  * NUL-terminated), occurrences[n_unitigs], circular[n_unitigs] (0 / 1). Any output may be NULL. KMI_ERR_INVALID when the map has
  * not been compacted since it last changed; KMI_ERR_OVERFLOW when a capacity is too small. */
 kmi_status kmi_dbg_unitigs_export_host(kmi_dbg *g, uint64_t *offsets, char *bases, uint64_t *occurrences, uint8_t *circular,

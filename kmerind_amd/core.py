@@ -409,6 +409,13 @@ class DeBruijnNodes:
     def build_device(self, dptr, nbytes):
         self.ctx.check(lib.kmi_dbg_build_dev(self.h, C.c_void_p(dptr), nbytes))
 
+    def build_dist(self, data, comm):
+        """Collective build over the ranks of `comm` (transport.GroupComm, or anything with the kmi_comm handle in `.h`): `data` is
+        this rank's record-aligned share of the input; every node goes to the rank KeyToRank gives its canonical k-mer
+        (kmi_dbg_build_dist_host). A rank with nothing passes b""."""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else np.ascontiguousarray(data, dtype=np.uint8)
+        self.ctx.check(lib.kmi_dbg_build_dist_host(self.h, comm.h, buf.ctypes.data_as(C.c_void_p), buf.size))
+
     def insert(self, kmers, edges):
         """insert(vector<pair<Kmer, uint8_t>>): tuples as the parser emits them, either strand"""
         kmers = _u64(kmers, self.n_words)
@@ -466,12 +473,20 @@ class DeBruijnNodes:
         lib.kmi_results_free(C.byref(r))
         return keys, vals
 
-    def unitigs(self, min_edge_count=1):
+    def unitigs(self, min_edge_count=1, comm=None):
         """Compacts the map on the device (kmi_dbg_compact; the definition is in include/kmerind_hip.h) ->
         (offsets: uint64[n + 1], bases: uint8[offsets[-1]] (ASCII letters), occurrences: uint64[n], circular: bool[n]).
-        Unitig i is bases[offsets[i]:offsets[i + 1]]."""
+        Unitig i is bases[offsets[i]:offsets[i + 1]]. With `comm` (transport.GroupComm, or anything with the kmi_comm handle in
+        `.h`) the call is collective (kmi_dbg_compact_dist_host): the graph is the union of the ranks' maps and the arrays are the
+        unitigs this rank holds; the counts over all ranks are left in `self.unitig_totals` as (unitigs, bases)."""
         nu, nb = C.c_uint64(), C.c_uint64()
-        self.ctx.check(lib.kmi_dbg_compact(self.h, int(min_edge_count), C.byref(nu), C.byref(nb)))
+        if comm is not None:
+            tu, tb = C.c_uint64(), C.c_uint64()
+            self.ctx.check(lib.kmi_dbg_compact_dist_host(self.h, comm.h, int(min_edge_count), C.byref(nu), C.byref(nb), C.byref(tu), C.byref(tb)))
+            self.unitig_totals = (tu.value, tb.value)
+        else:
+            self.ctx.check(lib.kmi_dbg_compact(self.h, int(min_edge_count), C.byref(nu), C.byref(nb)))
+            self.unitig_totals = (nu.value, nb.value)
         offsets = np.zeros(nu.value + 1, dtype=np.uint64)
         bases = np.zeros(max(nb.value, 1), dtype=np.uint8)
         occ = np.zeros(max(nu.value, 1), dtype=np.uint64)
@@ -481,9 +496,9 @@ class DeBruijnNodes:
                                                        nu.value, nb.value))
         return offsets, bases[:nb.value], occ[:nu.value], circ[:nu.value].astype(bool)
 
-    def unitig_sequences(self, min_edge_count=1):
+    def unitig_sequences(self, min_edge_count=1, comm=None):
         """the sequences of unitigs() as a list of bytes, in unitig order"""
-        return split_unitigs(*self.unitigs(min_edge_count)[:2])
+        return split_unitigs(*self.unitigs(min_edge_count, comm)[:2])
 
 
 def split_unitigs(offsets, bases):

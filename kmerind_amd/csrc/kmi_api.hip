@@ -282,6 +282,9 @@ kmi_status kmi_ctx_debug_counter(const kmi_ctx *ctx, uint32_t which, uint64_t *v
     case 2: *value = ctx->alloc_bytes; return KMI_OK;
     case 3: *value = ctx->alloc_calls; return KMI_OK;
     case 4: *value = ctx->alloc_reused; return KMI_OK;
+    case 5: *value = ctx->unitig_dist_rounds; return KMI_OK;
+    case 6: *value = ctx->unitig_dist_exchanges; return KMI_OK;
+    case 7: *value = ctx->unitig_dist_bytes; return KMI_OK;
     default: return KMI_ERR_INVALID;
   }
 }

@@ -380,6 +380,7 @@ struct kmi_dbg {
   size_t uni_bytes = 0;
   uint64_t n_unitigs = 0, n_unitig_bases = 0;
   uint32_t unitig_rounds = 0;   // pointer-jumping rounds of the last compaction
+  uint64_t unitig_exchanges = 0, unitig_bytes_sent = 0;   // ... over ranks (kmi_unitig_dist.h): exchanges, bytes this rank sent
 };
 
 namespace kmi {

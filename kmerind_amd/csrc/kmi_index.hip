@@ -4335,6 +4335,7 @@ static bool sk_rank_count(uint32_t p) { return p == 1u || p == 2u || p == 4u || 
 
 #include "kmi_debruijn.h"
 #include "kmi_unitig.h"
+#include "kmi_unitig_dist.h"
 #include "kmi_update.h"
 
 struct kmi_comm;
@@ -5788,6 +5789,28 @@ kmi_status kmi_dbg_compact(kmi_dbg *g, uint32_t min_edge_count, uint64_t *n_unit
   KMI_TRY(dbg_compact(g, min_edge_count));
   if (n_unitigs) *n_unitigs = g->n_unitigs;
   if (n_bases) *n_bases = g->n_unitig_bases;
+  return KMI_OK;
+}
+
+// ... of the union of the ranks' node maps (kmi_unitig_dist.h): collective
+kmi_status kmi_dbg_compact_dist_host(kmi_dbg *g, kmi_comm *comm, uint32_t min_edge_count, uint64_t *n_unitigs_local, uint64_t *n_bases_local,
+                                     uint64_t *n_unitigs_total, uint64_t *n_bases_total) {
+  if (!g) return KMI_ERR_INVALID;
+  if (n_unitigs_local) *n_unitigs_local = 0;
+  if (n_bases_local) *n_bases_local = 0;
+  if (n_unitigs_total) *n_unitigs_total = 0;
+  if (n_bases_total) *n_bases_total = 0;
+  KMI_TRY(dist_check(g->nodes, comm));
+  kmi_ctx *ctx = g->ctx;
+  uint64_t totals[2] = {0, 0};
+  if (kmi::comm_size(comm) == 1 && !ctx->force_dist) {
+    KMI_TRY(dbg_compact(g, min_edge_count));
+    totals[0] = g->n_unitigs; totals[1] = g->n_unitig_bases;
+  } else KMI_TRY(kmi::dbg_compact_dist(g, comm, min_edge_count, totals));
+  if (n_unitigs_local) *n_unitigs_local = g->n_unitigs;
+  if (n_bases_local) *n_bases_local = g->n_unitig_bases;
+  if (n_unitigs_total) *n_unitigs_total = totals[0];
+  if (n_bases_total) *n_bases_total = totals[1];
   return KMI_OK;
 }
 

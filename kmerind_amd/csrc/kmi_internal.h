@@ -60,6 +60,10 @@ enum WsSlot {
   WS_UNI_NEXT,        // ... next state of every (node, direction)
   WS_UNI_RANK,        // ... ranking records, two halves (ping-pong; the idle half holds the cycle pass and the scan)
   WS_UNI_NODE,        // ... device scalars, per-node direction and circular flags
+  WS_UNI_SCAN,        // unitig compaction over ranks (kmi_unitig_dist.h): (heads, bases) of every node and the scan's tile sums
+  WS_UNI_STAGE,       // ... staged 16-byte records of every state before they are grouped by rank; the link requests
+  WS_UNI_END,         // ... cycle candidates, then the end k-mer and end occurrences of every state
+  WS_UNI_CNT,         // ... records per destination rank, cursors, device scalars
   WS_NUM_SLOTS
 };
 
@@ -118,7 +122,8 @@ struct kmi_ctx {
   uint32_t sk_r2_win = 0;        // records of sk_reduce2's batch window (KMI_R2_WIN: test knob; 0: by the last build's duplication)
   uint64_t alloc_us = 0, alloc_bytes = 0, alloc_calls = 0, alloc_reused = 0;   // time inside hipMalloc / hipFree, bytes and calls that reached hipMalloc, blocks taken from the process-wide cache (kmi_ctx_debug_counter 1..4)
   uint32_t dist_pool_regrows = 0;     // times a build over ranks had to enlarge its receive pool (kmi_ctx_debug_counter: tests)
-  uint32_t dist_pool_pct = 100;       // the estimate itself, in percent (KMI_DIST_POOL_PCT: tests make it too small)
+  uint64_t unitig_dist_rounds = 0, unitig_dist_exchanges = 0, unitig_dist_bytes = 0;   // the last kmi_dbg_compact_dist_host: jumping rounds, exchanges, bytes this rank sent (kmi_ctx_debug_counter 5..7)
+  uint32_t dist_pool_pct = 100;      // the estimate itself, in percent (KMI_DIST_POOL_PCT: tests make it too small)
   uint64_t dist_pool_slack = 65536;   // records a rank's receive pool holds beyond the estimate of its share (KMI_DIST_POOL_SLACK: tests shrink it so that the pool has to grow)
   uint32_t dist_chunks = 4;      // record-aligned chunks of a rank's share in the build over ranks (exchange of one beside the front end of the next; KMI_DIST_CHUNKS)
   bool tuples_from_parse = true; // position / position + quality builds partition their tuples straight from the parse (kmi_tuples.h); KMI_TUPLES=extract: extract, then partition

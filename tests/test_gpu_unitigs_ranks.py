@@ -1,0 +1,403 @@
+"""Unitigs of a de Bruijn node map held over ranks (kmi_dbg_compact_dist_host / DeBruijnNodes.unitigs(comm=...)). The expected value
+is always the plain-Python model (tests/unitig_model.py) on the ORACLE's whole node map, never anything the GPU produced: the sorted
+union of the ranks' (sequence, occurrences, circular) must be the model's list, every rank's export must be well-formed, and the
+totals must be the model's counts on every rank. Two and four processes share the GPU over a gloo group (kmerind_amd/transport.py),
+as in test_gpu_dist_clayer.py; nodes are placed by KeyToRank of the canonical k-mer, so nearly every link of a path crosses ranks."""
+import ctypes as C
+import math
+import os
+import re
+import socket
+import subprocess
+import tempfile
+
+import numpy as np
+import pytest
+
+from tests import oracle as orc
+from tests import unitig_model as M
+
+pytestmark = pytest.mark.gpu
+GOLD = os.path.join(os.path.dirname(__file__), "golden", "data")
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+# ---- inputs ---------------------------------------------------------------------------------------------------------------------
+def _fastq(reads):
+    return "".join("@r%d\n%s\n+\n%s\n" % (i, r, "I" * len(r)) for i, r in enumerate(reads)).encode()
+
+
+def _fasta(records, width=80):
+    out = []
+    for i, r in enumerate(records):
+        out.append(">s%d\n" % i)
+        out += [r[j:j + width] + "\n" for j in range(0, len(r), width)]
+    return "".join(out).encode()
+
+
+def _genome(rng, n):
+    return "".join(np.array(list("ACGT"))[rng.integers(0, 4, n)])
+
+
+def _branching_reads(seed, k, n_reads=600):
+    """reads of a 3 000-base genome with a repeat of 3k inserted twice, 8 SNP variants, a poly-A stretch of 2k, both strands"""
+    rng = np.random.default_rng(seed)
+    g = _genome(rng, 3000)
+    rep = g[500:500 + 3 * k]
+    g = g[:1250] + rep + g[1250:2000] + rep + g[2000:] + "A" * (2 * k) + _genome(rng, 200)
+    snp = list(g)
+    for p in rng.integers(0, len(g), 8):
+        snp[p] = "ACGT"[(("ACGT".index(snp[p])) + 1) % 4]
+    snp = "".join(snp)
+    reads = []
+    for i in range(n_reads):
+        src = snp if i % 5 == 0 else g
+        p = int(rng.integers(0, len(src) - 100))
+        r = src[p:p + int(rng.integers(max(k, 60), 150))]
+        reads.append(M.revcomp(r) if rng.random() < 0.5 else r)
+    return _fastq(reads)
+
+
+def _circle_reads():
+    rng = np.random.default_rng(9)
+    circle = _genome(rng, 3000)
+    ring = circle + circle[:200]
+    reads = []
+    for p in range(0, len(circle), 50):
+        r = ring[p:p + 150]
+        reads.append(M.revcomp(r) if (p // 50) % 2 else r)
+    return circle, _fastq(reads)
+
+
+def _record_shares(data, world):
+    """contiguous shares of whole four-line records, one per rank"""
+    lines = data.rstrip(b"\n").split(b"\n")
+    n_rec = len(lines) // 4
+    cuts = [n_rec * r // world * 4 for r in range(world + 1)]
+    return [b"".join(ln + b"\n" for ln in lines[cuts[r]:cuts[r + 1]]) for r in range(world)]
+
+
+_MAPS = {}
+
+
+def _oracle_map(key, data, k, fmt=orc.FASTQ, exists=False):
+    """the oracle's node map of an input, computed once per module"""
+    if key not in _MAPS:
+        s = orc.kspec(k)
+        om = orc.DbgMap(s, exists_only=exists)
+        om.insert(*orc.dbg_parse(s, data, fmt))
+        _MAPS[key] = om.export(canonical=True)
+    return _MAPS[key]
+
+
+# ---- the ranks --------------------------------------------------------------------------------------------------------------------
+def _free_port():
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    p = s.getsockname()[1]
+    s.close()
+    return p
+
+
+def _compact(ctx, L, g, comm, t):
+    """this rank's result of the collective call through the Python surface, with the library's counters for it"""
+    from kmerind_amd.core import split_unitigs
+    off, bases, occ, circ = g.unitigs(t, comm=comm)
+    assert off.shape[0] == occ.shape[0] + 1 == circ.shape[0] + 1 and int(off[-1]) == bases.shape[0] and int(off[0]) == 0
+    v = C.c_uint64()
+    counters = []
+    for which in (5, 6, 7):
+        ctx.check(L.lib.kmi_ctx_debug_counter(ctx.h, which, C.byref(v)))
+        counters.append(v.value)
+    return dict(units=[(s.decode(), int(o), bool(c)) for s, o, c in zip(split_unitigs(off, bases), occ, circ)], totals=tuple(g.unitig_totals),
+                offsets=off.tolist(), rounds=counters[0], exchanges=counters[1], sent=counters[2])
+
+
+def _job_fastq(K, L, ctx, comm, rank, world, job):
+    g = K.DeBruijnNodes(ctx, K.make_config(job["k"]), exists_only=job.get("exists", False))
+    g.build_dist(job["parts"][rank], comm)
+    out = {}
+    if job.get("erase") is not None:
+        mine = np.ascontiguousarray(job["erase"][rank::world])
+        n = C.c_uint64()
+        ctx.check(L.lib.kmi_dbg_erase_dist_host(g.h, comm.h, mine.ctypes.data_as(C.c_void_p), mine.shape[0], C.byref(n)))
+        out["erased"] = n.value
+    for t in job["ts"]:
+        out[t] = _compact(ctx, L, g, comm, t)
+    out["local_size"] = g.local_size()
+    g.close()
+    return out
+
+
+def _job_fasta_range(K, L, ctx, comm, rank, world, job):
+    data, n = job["data"], len(job["data"])
+    lo, hi = n * rank // world, n * (rank + 1) // world
+    g = K.DeBruijnNodes(ctx, K.make_config(job["k"], seq_format="fasta"))
+    buf = np.frombuffer(data[lo:], dtype=np.uint8).copy()   # the rest of the file behind the rank's nominal range
+    need = C.c_int(0)
+    ctx.check(L.lib.kmi_dbg_build_fasta_range_dist_host(g.h, comm.h, buf.ctypes.data_as(C.c_void_p), buf.size, lo, hi - lo, 1, data[lo - 1] if lo else -1,
+                                                        C.byref(need)))
+    assert not need.value
+    out = {1: _compact(ctx, L, g, comm, 1), "local_size": g.local_size()}
+    g.close()
+    return out
+
+
+def _job_nothing(K, L, ctx, comm, rank, world, job):
+    g = K.DeBruijnNodes(ctx, K.make_config(job["k"]))
+    g.build_dist(job["parts"][rank], comm)
+    out = {"one": _compact(ctx, L, g, comm, 1), "local_size": g.local_size()}
+    g.clear()
+    out["empty"] = _compact(ctx, L, g, comm, 1)
+    g.close()
+    return out
+
+
+def _job_contract(K, L, ctx, comm, rank, world, job):
+    nul, nbl, nut, nbt = C.c_uint64(), C.c_uint64(), C.c_uint64(), C.c_uint64()
+
+    def dist_compact(h, t):
+        return L.lib.kmi_dbg_compact_dist_host(h, comm.h, t, C.byref(nul), C.byref(nbl), C.byref(nut), C.byref(nbt))
+
+    out = {}
+    g5 = K.DeBruijnNodes(ctx, K.make_config(21, "DNA5"))
+    g5.build_dist(job["parts"][rank], comm)
+    out["dna5"] = dist_compact(g5.h, 1)
+    g5.close()
+    g = K.DeBruijnNodes(ctx, K.make_config(job["k"]))
+    g.build_dist(job["parts"][rank], comm)
+    out["t0"] = dist_compact(g.h, 0)
+    out["export_after_t0"] = L.lib.kmi_dbg_unitigs_export_host(g.h, None, None, None, None, 0, 0)
+    out["first"] = _compact(ctx, L, g, comm, 1)
+    out["second"] = _compact(ctx, L, g, comm, 1)
+    out["null_outputs"] = L.lib.kmi_dbg_compact_dist_host(g.h, comm.h, 1, None, None, None, None)
+    out["export_ok"] = L.lib.kmi_dbg_unitigs_export_host(g.h, None, None, None, None, 0, 0)
+    out["plain_compact"] = L.lib.kmi_dbg_compact(g.h, 1, C.byref(nul), C.byref(nbl))   # a share is still refused
+    out["third"] = _compact(ctx, L, g, comm, 1)
+    mine = np.ascontiguousarray(job["erase"][rank::world])
+    n = C.c_uint64()
+    ctx.check(L.lib.kmi_dbg_erase_dist_host(g.h, comm.h, mine.ctypes.data_as(C.c_void_p), mine.shape[0], C.byref(n)))
+    out["export_after_erase"] = L.lib.kmi_dbg_unitigs_export_host(g.h, None, None, None, None, 0, 0)
+    g.close()
+    return out
+
+
+_JOBS = {"fastq": _job_fastq, "fasta_range": _job_fasta_range, "nothing": _job_nothing, "contract": _job_contract}
+
+
+def _worker(rank, world, port, job, ret):
+    import torch.distributed as dist
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        import kmerind_amd as K
+        from kmerind_amd import _lib as L
+        from kmerind_amd.transport import GroupComm
+        ctx = K.Context(0, rank=rank, nranks=world)
+        comm = GroupComm(ctx)
+        try:
+            ret[rank] = _JOBS[job["kind"]](K, L, ctx, comm, rank, world, job)
+        finally:
+            comm.close()
+            ctx.close()
+    finally:
+        dist.destroy_process_group()
+
+
+def _run(world, job):
+    import torch.multiprocessing as mp
+    assert world <= 4
+    ret = mp.Manager().dict()
+    mp.spawn(_worker, args=(world, _free_port(), job, ret), nprocs=world, join=True)
+    return [ret[r] for r in range(world)]
+
+
+def _check(res, key, exp):
+    """the union over ranks is the model's list; the totals are its counts on every rank"""
+    got = sorted(u for r in res for u in r[key]["units"])
+    assert len(got) == len(exp) and got == exp
+    for r in res:
+        assert r[key]["totals"] == (len(exp), sum(len(s) for s, _, _ in exp)), r[key]["totals"]
+    assert len({r[key]["rounds"] for r in res}) == 1 and len({r[key]["exchanges"] for r in res}) == 1   # the same collectives on every rank
+
+
+# ---- 1. branching reads, every word count -------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("k,world", [(15, 2), (21, 2), (31, 2), (32, 2), (33, 2), (63, 2), (31, 4), (63, 4)])
+def test_branching_reads_against_the_model(k, world):
+    data = _branching_reads(k, k)
+    keys, cnt = _oracle_map(("branching", k), data, k)
+    res = _run(world, dict(kind="fastq", k=k, parts=_record_shares(data, world), ts=[1, 2]))
+    assert sum(r["local_size"] for r in res) == keys.shape[0]
+    assert sum(1 for r in res if r["local_size"]) == world   # (every rank holds a share)
+    for t in (1, 2):
+        exp = M.unitigs(keys, cnt, k, t)
+        _check(res, t, exp)
+        if t == 1:
+            assert len(exp) > 10 and any(len(s) > 200 for s, _, _ in exp)   # (branches and long unitigs both)
+    assert sum(1 for r in res if r[1]["units"]) > 1   # unitigs are spread over the ranks
+
+
+# ---- 2. a cycle spread over ranks ---------------------------------------------------------------------------------------------------
+@pytest.mark.parametrize("world", [2, 4])
+def test_circle_is_one_circular_unitig_on_one_rank(world):
+    k = 31
+    circle, data = _circle_reads()
+    ext = circle + circle[:k - 1]
+    m = min(M.canonical(ext[i:i + k]) for i in range(len(circle)))
+    start = circle if m in ext else M.revcomp(circle)   # spelled from m in its stored orientation
+    i = (start + start[:k - 1]).find(m)
+    seq = (start + start)[i:i + len(circle) + k - 1]
+    exp = [(seq, 7200, True)]
+    assert len(seq) == 3030 and M.unitigs(*_oracle_map(("circle",), data, k), k) == exp
+    res = _run(world, dict(kind="fastq", k=k, parts=_record_shares(data, world), ts=[1]))
+    _check(res, 1, exp)
+    assert sorted(len(r[1]["units"]) for r in res) == [0] * (world - 1) + [1]
+    for r in res:
+        if not r[1]["units"]:
+            assert r[1]["offsets"] == [0]
+
+
+# ---- 3. one long path -------------------------------------------------------------------------------------------------------------
+def test_one_long_path_over_four_ranks():
+    k, world = 31, 4
+    genome = _genome(np.random.default_rng(2024), 30_000)
+    data = _fasta([genome])
+    n_nodes = len(genome) - k + 1
+    exp = [(min(genome, M.revcomp(genome)), n_nodes, False)]
+    assert M.unitigs(*_oracle_map(("path",), data, k, orc.FASTA), k) == exp
+    res = _run(world, dict(kind="fasta_range", k=k, data=data))
+    assert sum(r["local_size"] for r in res) == n_nodes
+    _check(res, 1, exp)
+    rounds = res[0][1]["rounds"]
+    assert math.ceil(math.log2(n_nodes)) <= rounds <= math.ceil(math.log2(2 * n_nodes)) + 1, rounds   # [15, 17]
+    assert res[0][1]["exchanges"] >= 2 * rounds + 4 and sum(r[1]["sent"] for r in res) > 0
+
+
+# ---- 4. ranks with nothing ----------------------------------------------------------------------------------------------------------
+def test_ranks_that_own_no_node_and_an_empty_graph():
+    read = "ACCGATTGCAGGTTACGGATC"
+    res = _run(4, dict(kind="nothing", k=21, parts=[_fastq([read]), b"", b"", b""]))
+    assert sorted(r["local_size"] for r in res) == [0, 0, 0, 1]
+    _check(res, "one", [(min(read, M.revcomp(read)), 1, False)])
+    _check(res, "empty", [])
+    for r in res:
+        assert r["empty"]["offsets"] == [0] and r["empty"]["totals"] == (0, 0)
+
+
+# ---- 5. EDGE_EXISTS map -------------------------------------------------------------------------------------------------------------
+def test_edge_exists_map_over_two_ranks():
+    k = 31
+    data = open(os.path.join(GOLD, "test.debruijn.small.fastq"), "rb").read()
+    exp = M.unitigs(*_oracle_map(("small-exists",), data, k, exists=True), k)
+    res = _run(2, dict(kind="fastq", k=k, parts=_record_shares(data, 2), ts=[1], exists=True))
+    _check(res, 1, exp)
+    assert exp and all(o == 0 for r in res for _, o, _ in r[1]["units"])
+
+
+# ---- 6. after a collective erase ----------------------------------------------------------------------------------------------------
+def test_after_a_collective_erase():
+    k = 31
+    data = _branching_reads(k, k)
+    keys, cnt = _oracle_map(("branching", k), data, k)
+    victims = np.ascontiguousarray(keys[::7])
+    keep = np.ones(keys.shape[0], bool)
+    keep[::7] = False
+    res = _run(2, dict(kind="fastq", k=k, parts=_record_shares(data, 2), ts=[1], erase=victims))
+    assert sum(r["erased"] for r in res) == victims.shape[0]
+    _check(res, 1, M.unitigs(keys[keep], cnt[keep], k))
+
+
+# ---- 7. golden FASTQ with N ---------------------------------------------------------------------------------------------------------
+def test_golden_fastq_with_n_over_two_ranks():
+    k = 21
+    data = open(os.path.join(GOLD, "natural.withN.fastq"), "rb").read()
+    keys, cnt = _oracle_map(("withN",), data, k)
+    res = _run(2, dict(kind="fastq", k=k, parts=_record_shares(data, 2), ts=[1, 2]))
+    for t in (1, 2):
+        _check(res, t, M.unitigs(keys, cnt, k, t))
+
+
+# ---- 8. one-rank communicator, forced-distributed: the numbering rule ---------------------------------------------------------------
+class _Comm:
+    def __init__(self, h):
+        self.h = h
+
+
+def test_one_rank_forced_distributed_gives_the_arrays_of_compact(monkeypatch):
+    import kmerind_amd as K
+    from kmerind_amd import _lib as L
+    k = 31
+    data = _branching_reads(k, k)
+    plain = K.Context(0)
+    g0 = K.DeBruijnNodes(plain, K.make_config(k))
+    g0.build(data)
+    exp = [a.copy() for a in g0.unitigs()]
+    g0.close()
+    plain.close()
+    monkeypatch.setenv("KMI_FORCE_DIST", "1")
+    ctx = K.Context(0, rank=0, nranks=1)
+    h = C.c_void_p()
+    ctx.check(L.lib.kmi_comm_create(ctx.h, None, C.byref(h)))
+    try:
+        g = K.DeBruijnNodes(ctx, K.make_config(k))
+        g.build(data)
+        got = g.unitigs(comm=_Comm(h))
+        assert len(exp[0]) > 10
+        for a, b in zip(got, exp):
+            assert a.dtype == b.dtype and a.shape == b.shape and (a == b).all()
+        assert g.unitig_totals == (len(exp[2]), len(exp[1]))
+        v = C.c_uint64()
+        ctx.check(L.lib.kmi_ctx_debug_counter(ctx.h, 6, C.byref(v)))
+        assert v.value > 0   # the exchanges ran, with the rank as its own peer
+        assert [s for s in g.unitig_sequences(comm=_Comm(h))] == K.core.split_unitigs(exp[0], exp[1])
+        g.close()
+    finally:
+        L.lib.kmi_comm_destroy(h)
+        ctx.close()
+
+
+# ---- 9. contract ------------------------------------------------------------------------------------------------------------------
+def test_contract_over_two_ranks():
+    from kmerind_amd import _lib as L
+    k = 31
+    data = _branching_reads(k, k)
+    keys, cnt = _oracle_map(("branching", k), data, k)
+    res = _run(2, dict(kind="contract", k=k, parts=_record_shares(data, 2), erase=np.ascontiguousarray(keys[:5])))
+    exp = M.unitigs(keys, cnt, k)
+    for r in res:
+        assert r["dna5"] == L.ERR_INVALID and r["t0"] == L.ERR_INVALID and r["export_after_t0"] == L.ERR_INVALID
+        assert r["null_outputs"] == L.OK and r["export_ok"] == L.OK
+        assert r["plain_compact"] == L.ERR_INVALID
+        assert r["first"]["units"] == r["second"]["units"] == r["third"]["units"] and r["first"]["offsets"] == r["second"]["offsets"]
+        assert r["export_after_erase"] == L.ERR_INVALID
+    _check(res, "first", exp)
+
+
+# ---- 10. the C++ facade: one rank through the collective code ----------------------------------------------------------------------
+def _read_fasta(path):
+    recs = []
+    for block in open(path).read().split(">")[1:]:
+        head, seq = block.split("\n", 1)
+        m = re.fullmatch(r"u(\d+) len=(\d+) occ=(\d+) circular=([01])", head)
+        assert m, head
+        seq = seq.replace("\n", "")
+        assert int(m.group(1)) == len(recs) and int(m.group(2)) == len(seq)
+        recs.append((seq, int(m.group(3)), m.group(4) == "1"))
+    return recs
+
+
+@pytest.mark.parametrize("name,fmt", [("test.debruijn.small.fastq", orc.FASTQ), ("natural.fasta", orc.FASTA)])
+def test_facade_example_through_the_collective_code(name, fmt):
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "examples"), "de_bruijn_unitigs_ranks"], stdout=subprocess.DEVNULL)
+    exe = os.path.join(ROOT, "examples", "de_bruijn_unitigs_ranks")
+    path = os.path.join(GOLD, name)
+    with tempfile.TemporaryDirectory() as d:
+        out = os.path.join(d, "u.fasta")
+        p = subprocess.run([exe, path, out], capture_output=True, text=True, timeout=300, env=dict(os.environ, KMI_FORCE_DIST="1"))
+        assert p.returncode == 0, p.stderr
+        got = _read_fasta(out)
+    exp = M.unitigs(*_oracle_map(("example", name), open(path, "rb").read(), 31, fmt), 31)
+    assert sorted(got) == exp
+    n, b = len(exp), sum(len(s) for s, _, _ in exp)
+    # (the summary is the last line: RCCL may print a version banner before it)
+    assert p.stdout.strip().split("\n")[-1] == "rank 0 of 1 unitigs %d bases %d total_unitigs %d total_bases %d" % (n, b, n, b)

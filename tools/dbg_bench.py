@@ -6,7 +6,12 @@ file, and kmi_dbg_build_fasta_range_dist_host over a one-rank communicator on th
   python tools/dbg_bench.py --fasta [genome] [k]
 Unitigs: the node map of the FASTQ input above (default: config 2's, 10 M reads of a 100 Mbp genome, k = 31), then kmi_dbg_compact
 timed warm, with its pointer-jumping rounds, per-kernel times and unitig statistics.
-  python tools/dbg_bench.py --unitigs [reads] [genome] [k]"""
+  python tools/dbg_bench.py --unitigs [reads] [genome] [k]
+Unitigs over ranks: N processes share the GPU over a gloo group (kmerind_amd/transport.py, as tests/test_gpu_dist_clayer.py starts
+them); every rank builds its share of the reads collectively, then kmi_dbg_compact_dist_host is timed warm, with its jumping rounds,
+exchanges, bytes exchanged per node and per-kernel times of rank 0. The transport stages every message through pinned host memory
+and gloo, so these are not RCCL numbers. Default input: 1 M reads of a 10 Mbp genome (1e7 nodes), k = 31. --out FILE: the figures as JSON.
+  python tools/dbg_bench.py --unitigs --ranks N [--out FILE] [reads] [genome] [k]"""
 import ctypes as C
 import os
 import sys
@@ -117,9 +122,98 @@ def main_unitigs(argv):
           % (nu.value, nb.value, int(circ.sum()), int(lens[0]) if lens.size else 0, float(lens.mean()) if lens.size else 0.0, n50, int(occ.sum())))
 
 
+def _ranks_worker(rank, world, port, n_reads, genome, k, steps, ret):
+    import torch.distributed as dist
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from kmerind_amd import _lib as L
+        from kmerind_amd.transport import GroupComm
+        ctx = K.Context(0, rank=rank, nranks=world)
+        comm = GroupComm(ctx)
+        lo, hi = n_reads * rank // world, n_reads * (rank + 1) // world
+        host = np.asarray(K.synth_fastq(seed=2, genome_len=genome, n_reads=hi - lo, first_read=lo))
+        g = K.DeBruijnNodes(ctx, K.make_config(k))
+        t0 = time.perf_counter()
+        g.build_dist(host, comm)
+        build_s = time.perf_counter() - t0
+        del host
+        if rank == 0:
+            print("built over %d ranks in %.1f s; rank 0 holds %d nodes" % (world, build_s, g.local_size()), flush=True)
+        out = [C.c_uint64() for _ in range(4)]
+
+        def compact():
+            ctx.check(L.lib.kmi_dbg_compact_dist_host(g.h, comm.h, 1, *[C.byref(v) for v in out]))
+        dist.barrier()
+        t0 = time.perf_counter()
+        compact()
+        cold = time.perf_counter() - t0
+        if rank == 0:
+            print("first compaction %.2f s" % cold, flush=True)
+        ctx.profile(True); ctx.profile_reset()
+        dist.barrier()
+        t0 = time.perf_counter()
+        for _ in range(steps):
+            compact()
+        warm = (time.perf_counter() - t0) / steps
+        prof = {p["name"]: round(p["total_ms"] / steps, 3) for p in sorted(ctx.profile_get(), key=lambda p: -p["total_ms"]) if p["launches"]}
+        ctx.profile(False)
+        cnt = []
+        v = C.c_uint64()
+        for which in (5, 6, 7):
+            ctx.check(L.lib.kmi_ctx_debug_counter(ctx.h, which, C.byref(v)))
+            cnt.append(v.value)
+        ret[rank] = dict(nodes=g.local_size(), cold_s=cold, warm_s=warm, rounds=cnt[0], exchanges=cnt[1], bytes_sent=cnt[2], unitigs_local=out[0].value,
+                         unitigs_total=out[2].value, bases_total=out[3].value, kernels_ms=prof, build_s=build_s)
+        g.close()
+        comm.close()
+        ctx.close()
+    finally:
+        dist.destroy_process_group()
+
+
+def main_unitigs_ranks(argv):
+    import json
+    import socket
+    import torch.multiprocessing as mp
+    world = int(argv[0])
+    argv = argv[1:]
+    out_path = None
+    if argv and argv[0] == "--out":
+        out_path, argv = argv[1], argv[2:]
+    n_reads = int(argv[0]) if len(argv) > 0 else 1_000_000
+    genome = int(argv[1]) if len(argv) > 1 else 10_000_000
+    k = int(argv[2]) if len(argv) > 2 else 31
+    steps = 2
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    ret = mp.Manager().dict()
+    mp.spawn(_ranks_worker, args=(world, port, n_reads, genome, k, steps, ret), nprocs=world, join=True)
+    res = [ret[r] for r in range(world)]
+    nodes = sum(r["nodes"] for r in res)
+    sent = sum(r["bytes_sent"] for r in res)
+    summary = dict(ranks=world, k=k, reads=n_reads, genome=genome, nodes=nodes, nodes_per_rank=[r["nodes"] for r in res],
+                   warm_ms_per_rank=[round(r["warm_s"] * 1e3, 1) for r in res], cold_ms_rank0=round(res[0]["cold_s"] * 1e3, 1), steps=steps,
+                   rounds=res[0]["rounds"], exchanges=res[0]["exchanges"], bytes_exchanged=sent, bytes_per_node=round(sent / max(nodes, 1), 1),
+                   unitigs_total=res[0]["unitigs_total"], bases_total=res[0]["bases_total"], unitigs_per_rank=[r["unitigs_local"] for r in res],
+                   kernels_ms_rank0=res[0]["kernels_ms"], transport="gloo over pinned host staging (not RCCL)")
+    print("unitigs over %d ranks (gloo transport, pinned host staging: not RCCL), k=%d, %d reads over %d bp, %d nodes: kmi_dbg_compact_dist_host "
+          "%.1f ms warm on the slowest rank (mean of %d), %d jumping rounds, %d exchanges, %.1f bytes exchanged per node"
+          % (world, k, n_reads, genome, nodes, max(summary["warm_ms_per_rank"]), steps, summary["rounds"], summary["exchanges"], summary["bytes_per_node"]))
+    print(json.dumps(summary))
+    if out_path:
+        with open(out_path, "w") as f:
+            json.dump(summary, f, indent=1)
+            f.write("\n")
+
+
 def main():
     if len(sys.argv) > 1 and sys.argv[1] == "--fasta":
         return main_fasta(sys.argv[2:])
+    if len(sys.argv) > 3 and sys.argv[1] == "--unitigs" and sys.argv[2] == "--ranks":
+        return main_unitigs_ranks(sys.argv[3:])
     if len(sys.argv) > 1 and sys.argv[1] == "--unitigs":
         return main_unitigs(sys.argv[2:])
     n_reads = int(sys.argv[1]) if len(sys.argv) > 1 else 2_000_000
