@@ -688,6 +688,37 @@ class Index {
     ::kmerind::check(ctx, kmi_index_build_dist_host(idx, rccl, bytes, n_bytes, file_offset));
   }
 
+  // ---- queries in the caller's order (no counterpart in the reference: count() / find() answer once per distinct key, unordered).
+  // Count indexes on one rank. lookup: out[i] = the count stored for query[i]'s transformed key, 0 when absent.
+  std::vector<uint32_t> lookup(std::vector<KmerType> const &query) const {
+    static_assert(MapType::index_kind == KMI_INDEX_COUNT, "lookup() is a member of the count index");
+    if (comm.size() > 1) throw std::invalid_argument("lookup() answers from one rank's entries: size() > 1 is not supported");
+    std::vector<uint32_t> out(query.size());
+    ::kmerind::check(ctx, kmi_index_lookup_host(idx, detail::words_of(query), query.size(), out.data()));
+    return out;
+  }
+  // profile_reads: one kmi_read_profile row per record of a FASTQ file, in file order -- how many of the read's k-mers the index
+  // holds, how many of them at least `solid` times, their lowest / highest / summed count. The file is read as build_posix reads it.
+  std::vector<kmi_read_profile> profile_reads(const std::string &filename, uint32_t solid = 2) const {
+    static_assert(MapType::index_kind == KMI_INDEX_COUNT, "profile_reads() is a member of the count index");
+    if (comm.size() > 1) throw std::invalid_argument("profile_reads() answers from one rank's entries: size() > 1 is not supported");
+    if (detail::format_of(filename) != KMI_FMT_FASTQ) throw std::invalid_argument("profile_reads() reads FASTQ files");
+    const std::vector<uint8_t> bytes = detail::read_whole_file(filename);
+    size_t cap = 2;   // every record but the last ends four lines
+    for (uint8_t c : bytes) cap += (c == '\n');
+    cap = cap / 4 + 2;
+    std::vector<kmi_read_profile> out(cap);
+    uint64_t n = 0;
+    kmi_status st = kmi_index_profile_reads_host(idx, bytes.data(), bytes.size(), solid, out.data(), out.size(), &n);
+    if (st == KMI_ERR_OVERFLOW && n > out.size()) {   // (lines that end in a bare carriage return)
+      out.resize((size_t)n);
+      st = kmi_index_profile_reads_host(idx, bytes.data(), bytes.size(), solid, out.data(), out.size(), &n);
+    }
+    ::kmerind::check(ctx, st);
+    out.resize((size_t)n);
+    return out;
+  }
+
   kmi_ctx *context() const { return ctx; }
   const kmi_config &config() const { return cfg; }
 

@@ -98,7 +98,9 @@ kmi_status kmi_ctx_reset_hints(kmi_ctx *ctx);
 /* counters the library keeps for its tests and for diagnosis (no reference counterpart). which = 0: times a build over ranks had to
  * enlarge its receive pool (kmi_index_build_dist_dev); 1: microseconds this context has spent inside hipMalloc / hipFree; 2: bytes
  * and 3: calls that reached hipMalloc; 4: blocks taken from the process-wide cache instead; 5: pointer-jumping rounds, 6: exchanges
- * and 7: bytes this rank sent in the context's last kmi_dbg_compact_dist_host */
+ * and 7: bytes this rank sent in the context's last kmi_dbg_compact_dist_host; 8: the largest number of passes a bucket needed in
+ * the context's last kmi_index_lookup_* / kmi_index_profile_reads_* (1 when every bucket's entries fit one table; 0: no bucket was
+ * looked at) */
 kmi_status kmi_ctx_debug_counter(const kmi_ctx *ctx, uint32_t which, uint64_t *value);
 /* A destroyed context leaves its large device blocks (workspace, spare index arrays: >= 1 MB each, 96 GB / 64 blocks at most) in a
  * process-wide cache per device, where the next context of that device finds them: its first build then does not wait for
@@ -435,6 +437,51 @@ kmi_status kmi_index_size_dist(kmi_index *idx, kmi_comm *comm, uint64_t *n);
 enum { KMI_UPDATE_ADD = 0, KMI_UPDATE_MAX = 1, KMI_UPDATE_MIN = 2, KMI_UPDATE_ASSIGN = 3 };
 kmi_status kmi_index_update_pairs_host(kmi_index *idx, const uint64_t *records, size_t n, uint32_t op, uint64_t *n_updated);
 kmi_status kmi_index_update_pairs_dev(kmi_index *idx, const uint64_t *records_dev, size_t n, uint32_t op, uint64_t *n_updated);
+
+/* ---- queries in the caller's order (no counterpart in the reference: its count() / find() answer once per distinct transformed
+ * key, in no particular order, and it has no per-read query at all)
+ * Count indexes only (KMI_INDEX_COUNT); a position index gives KMI_ERR_INVALID. Every k-mer shape a count index takes (one to four
+ * words; 2-, 3- and 4-bit alphabets), both layouts (placement hash, and the minimizer layout a super-k-mer build leaves), dense and
+ * sparse indexes alike. The index is not changed (a sparse index stays sparse); an empty index answers 0 everywhere. One rank's
+ * entries only: an index spread over ranks answers for this rank's share.
+ *
+ * lookup: counts[i] = the count stored for InputTransform(queries[i]) (the transform find() applies), 0 when it is not in the
+ * index. One answer per query, in query order; a key asked twice is answered twice. nq == 0 is fine.
+ * KMI_ERR_OVERFLOW: a bucket of the index could not be looked up within the library's pass limit (as for the other queries). */
+kmi_status kmi_index_lookup_dev (kmi_index *idx, const uint64_t *queries_dev, size_t nq, uint32_t *counts_dev);
+kmi_status kmi_index_lookup_host(kmi_index *idx, const uint64_t *queries,     size_t nq, uint32_t *counts);
+
+typedef struct {
+  uint64_t seq_offset;  /* byte offset, from bytes_dev, of the read's first sequence character (n_bytes when the record has no sequence line) */
+  uint64_t sum_counts;  /* sum of the looked-up counts over the read's k-mers */
+  uint32_t n_kmers;     /* windows the index's parser yields for this read (KMI_SEQ_ALL) */
+  uint32_t n_present;   /* of those, in the index */
+  uint32_t n_solid;     /* of those, with count >= solid_threshold */
+  uint32_t lowest;      /* min over the read's k-mers, an absent k-mer counting 0; 0 when n_kmers == 0 */
+  uint32_t highest;     /* max, likewise */
+  uint32_t reserved;    /* 0 */
+} kmi_read_profile;     /* 40 bytes */
+
+/* profile_reads: one row per FASTQ record of the record-aligned buffer, in file order (row i = record i, records without a k-mer
+ * included).
+ *  - Windows. The k-mers of a read are exactly those kmi_extract_dev yields for the same bytes with the index's kmi_config and
+ *    KMI_SEQ_ALL (the index's own sequence filter is not consulted); each goes through the index's InputTransform, as for find().
+ *  - Format. FASTQ only: an index whose sequence format is FASTA gives KMI_ERR_INVALID. Malformed input gives KMI_ERR_PARSE with the
+ *    message the builds give.
+ *  - Arguments. solid_threshold == 0 gives KMI_ERR_INVALID. bytes_dev may be unaligned. n_bytes == 0 is fine (*n_reads = 0).
+ *  - Capacity. *n_reads is always the number of records; capacity < *n_reads gives KMI_ERR_OVERFLOW, the first `capacity` rows are
+ *    written and nothing past them.
+ *  - Long reads. A read with a k-mer that starts more than 65535 bytes into its record gives KMI_ERR_OVERFLOW (the extract pass
+ *    numbers its tuples with the reference's 16-bit in-record offset and refuses such a record); it never gives wrong rows.
+ *  - Batches. The input is worked on in record-aligned batches of at most KMI_PROFILE_BATCH bytes (environment, read when the context
+ *    is created; default 256 MiB, at least 4096; a batch grows to hold at least one record), so the workspace is that of one batch
+ *    whatever the size of the input. The rows do not depend on the batch size.
+ * kmi_ctx_debug_counter 8 tells how many passes the fullest bucket needed; KMI_LOOKUP_CAP (environment, at context creation; 64 ..
+ * the table's own size) shrinks the lookup table so that tests reach several passes with a small index. */
+kmi_status kmi_index_profile_reads_dev (kmi_index *idx, const uint8_t *bytes_dev, size_t n_bytes, uint32_t solid_threshold,
+                                        kmi_read_profile *out_dev, size_t capacity, uint64_t *n_reads);
+kmi_status kmi_index_profile_reads_host(kmi_index *idx, const uint8_t *bytes, size_t n_bytes, uint32_t solid_threshold,
+                                        kmi_read_profile *out, size_t capacity, uint64_t *n_reads);
 
 /* ---- a count index over 2, 4 or 8 ranks through exchanged super-k-mers ---------------
  * The reference's distributed insert sends every k-mer to KeyToRank(k-mer) (8 bytes per k-mer over the wire,

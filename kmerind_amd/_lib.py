@@ -144,6 +144,10 @@ SIGNATURES = {
     "kmi_index_size_dist": (C.c_int, [_P, _P, C.POINTER(_u64)]),
     "kmi_index_update_pairs_host": (C.c_int, [_P, _P, _sz, _u32, C.POINTER(_u64)]),
     "kmi_index_update_pairs_dev": (C.c_int, [_P, _P, _sz, _u32, C.POINTER(_u64)]),
+    "kmi_index_lookup_dev": (C.c_int, [_P, _P, _sz, _P]),
+    "kmi_index_lookup_host": (C.c_int, [_P, _P, _sz, _P]),
+    "kmi_index_profile_reads_dev": (C.c_int, [_P, _P, _sz, _u32, _P, _sz, C.POINTER(_u64)]),
+    "kmi_index_profile_reads_host": (C.c_int, [_P, _P, _sz, _u32, _P, _sz, C.POINTER(_u64)]),
     "kmi_index_sk_produce_dev": (C.c_int, [_P, _P, _sz, _u32, _P, _sz, C.POINTER(_P), C.POINTER(_u64), _P, C.POINTER(C.c_int)]),
     "kmi_index_sk_consume_dev": (C.c_int, [_P, _P, _sz, _u32]),
     "kmi_route_owner_dev": (C.c_int, [_P, _CFG, _P, _sz, _u32, _P, _P]),

@@ -165,6 +165,12 @@ class Context:
                               part["index_shift"], 0)
         self.check(lib.kmi_ctx_set_fasta_partition(self.h, C.byref(fp)))
 
+    def debug_counter(self, which):
+        """kmi_ctx_debug_counter: the counters the library keeps for its tests and for diagnosis"""
+        v = C.c_uint64()
+        self.check(lib.kmi_ctx_debug_counter(self.h, which, C.byref(v)))
+        return v.value
+
     # ---- profiling
     def profile(self, on=True):
         self.check(lib.kmi_profile_enable(self.h, int(on)))
@@ -178,6 +184,12 @@ class Context:
         self.check(lib.kmi_profile_get(self.h, arr, 64, C.byref(n)))
         return [{"name": arr[i].name.decode(), "total_ms": arr[i].total_ms, "launches": arr[i].launches,
                  "units": arr[i].units} for i in range(min(n.value, 64))]
+
+
+# kmi_read_profile (kmerind_hip.h), field for field: 40 bytes per read
+READ_PROFILE_DTYPE = np.dtype([("seq_offset", np.uint64), ("sum_counts", np.uint64), ("n_kmers", np.uint32), ("n_present", np.uint32),
+                               ("n_solid", np.uint32), ("lowest", np.uint32), ("highest", np.uint32), ("reserved", np.uint32)])
+assert READ_PROFILE_DTYPE.itemsize == 40
 
 
 def num_buckets():
@@ -312,6 +324,45 @@ class CountIndex:
         q = _u64(q, self.n_words)
         n = C.c_uint64()
         self.ctx.check(lib.kmi_index_erase_host(self.h, q.ctypes.data_as(C.c_void_p), q.shape[0], C.byref(n)))
+        return n.value
+
+    # ---- queries in the caller's order (no reference counterpart; a position index refuses them)
+    def lookup(self, q):
+        """counts[i] = the count stored for the transformed q[i], 0 when absent: one answer per query, in query order"""
+        q = _u64(q, self.n_words)
+        out = np.zeros(q.shape[0], dtype=np.uint32)
+        self.ctx.check(lib.kmi_index_lookup_host(self.h, q.ctypes.data_as(C.c_void_p), q.shape[0], out.ctypes.data_as(C.c_void_p)))
+        return out
+
+    def lookup_device(self, q_dptr, n, out_dptr):
+        """q_dptr: n k-mers of n_words u64 on the device; out_dptr: n u32 counts"""
+        self.ctx.check(lib.kmi_index_lookup_dev(self.h, C.c_void_p(q_dptr), n, C.c_void_p(out_dptr)))
+
+    def profile_reads(self, data, solid=2):
+        """one row (READ_PROFILE_DTYPE) per FASTQ record of `data`, in file order: how many of the read's k-mers the index
+        holds, how many of them at least `solid` times, and the lowest / highest / summed count"""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else \
+            np.ascontiguousarray(data, dtype=np.uint8)
+        n = C.c_uint64()
+        cap = int(np.count_nonzero((buf == 10) | (buf == 13))) // 4 + 2   # (every record but the last ends four lines)
+        while True:
+            out = np.zeros(cap, dtype=READ_PROFILE_DTYPE)
+            st = lib.kmi_index_profile_reads_host(self.h, buf.ctypes.data_as(C.c_void_p), buf.size, solid,
+                                                  out.ctypes.data_as(C.c_void_p), cap, C.byref(n))
+            if st == L.ERR_OVERFLOW and n.value > cap:
+                cap = n.value
+                continue
+            self.ctx.check(st)
+            return out[:n.value].copy()
+
+    def profile_reads_device(self, dptr, nbytes, out_dptr, capacity, solid=2):
+        """dptr: FASTQ bytes on the device; out_dptr: room for `capacity` rows of 40 bytes -> number of records"""
+        n = C.c_uint64()
+        st = lib.kmi_index_profile_reads_dev(self.h, C.c_void_p(dptr), nbytes, solid, C.c_void_p(out_dptr), capacity, C.byref(n))
+        if st != L.OK:
+            err = L.KmiError(st, (lib.kmi_last_error(self.ctx.h) or b"").decode())
+            err.n_reads = n.value
+            raise err
         return n.value
 
 

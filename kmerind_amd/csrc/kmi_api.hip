@@ -250,6 +250,8 @@ kmi_status kmi_ctx_create(int device, int rank, int nranks, void *stream, kmi_ct
   if (const char *mr = getenv("KMI_FRONT_MIN_RANGE")) { ctx->front_min_range = strtoull(mr, nullptr, 10); ctx->front_min_range = (ctx->front_min_range + 4095) / 4096 * 4096; if (!ctx->front_min_range) ctx->front_min_range = 4096; }
   if (const char *sm = getenv("KMI_SPARSE_MIN")) ctx->sparse_min = strtoull(sm, nullptr, 10);
   if (const char *fd = getenv("KMI_FORCE_DIST")) ctx->force_dist = atoi(fd) != 0;
+  if (const char *lc = getenv("KMI_LOOKUP_CAP")) { ctx->lookup_cap = (uint32_t)strtoul(lc, nullptr, 10); if (ctx->lookup_cap < 64) ctx->lookup_cap = 64; }   // (the upper bound is the table's: kmi_lookup.h)
+  if (const char *pb = getenv("KMI_PROFILE_BATCH")) { ctx->profile_batch = strtoull(pb, nullptr, 10); if (ctx->profile_batch < 4096) ctx->profile_batch = 4096; }
   ctx->device = device; ctx->rank = rank; ctx->nranks = nranks; ctx->stream = (hipStream_t)stream;
   if (hipMalloc((void **)&ctx->d_flags, sizeof(uint32_t) * 64) != hipSuccess ||
       hipMalloc((void **)&ctx->d_totals, sizeof(uint64_t) * (16 + 256)) != hipSuccess ||
@@ -285,6 +287,7 @@ kmi_status kmi_ctx_debug_counter(const kmi_ctx *ctx, uint32_t which, uint64_t *v
     case 5: *value = ctx->unitig_dist_rounds; return KMI_OK;
     case 6: *value = ctx->unitig_dist_exchanges; return KMI_OK;
     case 7: *value = ctx->unitig_dist_bytes; return KMI_OK;
+    case 8: *value = ctx->lookup_npass; return KMI_OK;
     default: return KMI_ERR_INVALID;
   }
 }

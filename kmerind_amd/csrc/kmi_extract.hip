@@ -645,6 +645,38 @@ __global__ __launch_bounds__((ExCfg<NW, BITS>::NT)) void fastq_extract_kernel(
   }
 }
 
+// The sequence line of EVERY record, for a per-read pass over the tuples (ReadScan): the extract pass fills a read's descriptor
+// from its first window, so a read shorter than k has none. One wavefront per scan tile ranks the line starts of the tile's EOL
+// bitmap words (a line start is a non-EOL byte behind an EOL or at the buffer's start) from the tile's line base; the line with
+// index 4 r + 1 is the sequence line of record r.
+__global__ __launch_bounds__(256) void fastq_seq_starts_kernel(const uint32_t *__restrict__ eolw, uint64_t n_words, uint64_t n_tiles, uint32_t tile_words,
+                                                              const uint32_t *__restrict__ line_base, ReadDesc *__restrict__ reads, uint64_t n_reads) {
+  const uint64_t n_waves = (uint64_t)gridDim.x * (blockDim.x / kWave);
+  const uint32_t lane = lane_id();
+  for (uint64_t t = (uint64_t)blockIdx.x * (blockDim.x / kWave) + wave_id(); t < n_tiles; t += n_waves) {
+    const uint64_t g0 = t * tile_words;
+    uint32_t cur = line_base[t];
+    uint32_t carry = g0 > 0 ? (eolw[g0 - 1] >> 31) : 1u;   // EOL status of the byte before the tile
+    for (uint32_t w0 = 0; w0 < tile_words; w0 += kWave) {
+      const uint64_t g = g0 + w0 + lane;
+      const uint32_t w = (w0 + lane < tile_words && g < n_words) ? eolw[g] : 0xffffffffu;
+      uint32_t prev = __shfl_up(w >> 31, 1, kWave);
+      if (lane == 0) prev = carry;
+      uint32_t ls = ~w & ((w << 1) | prev);
+      const uint32_t c = (uint32_t)__builtin_popcount(ls);
+      const uint32_t inc = wave_inclusive_scan(c);
+      uint32_t idx = cur + inc - c;
+      while (ls) {
+        const uint64_t r = (uint64_t)(idx - 1u) >> 2;
+        if ((idx & 3u) == 1u && r < n_reads) reads[r].seq_pos = g * 32 + (uint32_t)__builtin_ctz(ls);
+        ++idx; ls &= ls - 1u;
+      }
+      cur += __shfl(inc, kWave - 1, kWave);
+      carry = __shfl(w >> 31, kWave - 1, kWave);
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Sequence filters (the SeqIterType argument of read_file_* / build_*, filtered_sequence_iterator.hpp): the window-break
 // bitmap. NSplitSequencesIterator cuts a sequence at every 'N' / 'n' (NCharFilter, :429-440), so a k-mer window is
@@ -870,7 +902,7 @@ template <int NW, int BITS>
 static kmi_status extract_run_impl(kmi_ctx *ctx, const kmi_config *cfg, const uint8_t *bytes_dev, size_t n_bytes,
                                    KShape shape, uint64_t file_offset, uint64_t *out_kmers_dev, uint64_t *out_ids_dev,
                                    float *out_quals_dev, size_t out_capacity, bool apply_strand, bool scan_done, uint64_t *n_tuples,
-                                   uint64_t *n_seqs, uint32_t rec_words, bool edges) {
+                                   uint64_t *n_seqs, uint32_t rec_words, bool edges, ReadScan *read_scan) {
   using Cfg = ExCfg<NW, BITS>;
   // rec_words != 0: out_kmers_dev is a record buffer (key words, id[, quality bits]) of rec_words words per tuple
   const uint32_t kstride = rec_words ? rec_words : (uint32_t)NW, istride = rec_words ? rec_words : 1u;
@@ -883,7 +915,8 @@ static kmi_status extract_run_impl(kmi_ctx *ctx, const kmi_config *cfg, const ui
     ProfScope ps(ctx, "fastq_extract", n_bytes);
     const bool canonical = apply_strand && cfg->strand != KMI_STRAND_SINGLE;
     ReadDesc *reads = nullptr;
-    if (want_quals) {
+    uint64_t n_desc = 0;
+    if (want_quals || read_scan) {
       // one descriptor slot per sequence (totals[2] of the scan), empty until the read's first window fills it
       uint64_t n_seq_now = 0;
       KMI_HIP(ctx, hipMemcpyAsync(&n_seq_now, ctx->d_totals + 2, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
@@ -891,7 +924,15 @@ static kmi_status extract_run_impl(kmi_ctx *ctx, const kmi_config *cfg, const ui
       void *pr;
       KMI_TRY(ws_get(ctx, WS_READS, sizeof(ReadDesc) * (n_seq_now + 16), &pr));
       reads = (ReadDesc *)pr;
+      n_desc = n_seq_now + 16;
       KMI_HIP(ctx, hipMemsetAsync(reads, 0xff, sizeof(ReadDesc) * (n_seq_now + 16), ctx->stream));
+    }
+    if (read_scan) {
+      if (!want_ids || edges) return set_err(ctx, KMI_ERR_INVALID, "read descriptors come with the ids of the extract pass");
+      hipLaunchKernelGGL(fastq_seq_starts_kernel, dim3((unsigned)std::min<uint64_t>((r.n_tiles + 3) / 4, 2048)), dim3(256), 0, ctx->stream,
+                         (const uint32_t *)r.packed.eol, (uint64_t)(r.packed.n_cover / 32), r.n_tiles, (uint32_t)(Cfg::TILE / 32),
+                         (const uint32_t *)r.line_base, reads, n_desc);
+      read_scan->reads = reads; read_scan->eolw = (const uint32_t *)r.packed.eol; read_scan->n_eol_words = r.packed.n_cover / 32;
     }
     if (want_ids) {
       hipLaunchKernelGGL((fastq_extract_kernel<NW, BITS, true>), dim3((unsigned)r.n_tiles), dim3(Cfg::NT), 0, ctx->stream,
@@ -916,6 +957,7 @@ static kmi_status extract_run_impl(kmi_ctx *ctx, const kmi_config *cfg, const ui
   uint32_t fl[4] = {0, 0, 0, 0};
   KMI_HIP(ctx, hipMemcpyAsync(fl, ctx->d_flags, sizeof(fl), hipMemcpyDeviceToHost, ctx->stream));
   KMI_TRY(read_totals(ctx, n_tuples, n_seqs));
+  if (read_scan) read_scan->n_lines = ctx->h_totals[0];
   if (fl[1]) return set_err(ctx, KMI_ERR_OVERFLOW, "extract: output capacity too small");
   if (fl[3]) return set_err(ctx, KMI_ERR_OVERFLOW, "ShortSequenceKmerId increment overflow (k-mer more than 65535 bytes into its record)");
   return KMI_OK;
@@ -1051,7 +1093,8 @@ kmi_status extract_count(kmi_ctx *ctx, const kmi_config *cfg, const uint8_t *byt
 
 kmi_status extract_run(kmi_ctx *ctx, const kmi_config *cfg, const uint8_t *bytes_dev, size_t n_bytes,
                        uint64_t file_offset, uint64_t *out_kmers_dev, uint64_t *out_ids_dev, size_t out_capacity,
-                       bool apply_strand, bool scan_done, uint64_t *n_tuples, uint64_t *n_seqs, float *out_quals_dev, uint32_t rec_words, uint32_t edges) {
+                       bool apply_strand, bool scan_done, uint64_t *n_tuples, uint64_t *n_seqs, float *out_quals_dev, uint32_t rec_words, uint32_t edges,
+                       ReadScan *read_scan) {
   // edges (records): EDGES_NODE -- the value word of every record is 1 | edge byte << 32 and the key the smaller strand (kmi_debruijn.h);
   // EDGES_PARSED (FASTA) -- the value word is the edge byte and the key stays as parsed
   // rec_words != 0: out_kmers_dev takes whole records -- key words, id, and with rec_words == n_words + 2 the quality's float
@@ -1063,12 +1106,14 @@ kmi_status extract_run(kmi_ctx *ctx, const kmi_config *cfg, const uint8_t *bytes
   if ((out_quals_dev && !out_ids_dev && !rec_words) || ((out_quals_dev || rec_words == shape.n_words + 2u) && cfg->seq_format != KMI_FMT_FASTQ))
     return set_err(ctx, KMI_ERR_INVALID, "k-mer qualities need FASTQ input and are produced together with the ids");
   if (edges && rec_words != shape.n_words + 1u) return set_err(ctx, KMI_ERR_INVALID, "edge tuples are records of n_words + 1 words");
+  if (read_scan && (cfg->seq_format != KMI_FMT_FASTQ || cfg->seq_filter != KMI_SEQ_ALL))
+    return set_err(ctx, KMI_ERR_INVALID, "read descriptors are made for unfiltered FASTQ input");
   if (cfg->seq_format == KMI_FMT_FASTA)
     return fasta_extract(ctx, cfg, bytes_dev, n_bytes, shape, file_offset, out_kmers_dev, out_ids_dev, out_capacity, apply_strand, false,
                          n_tuples, n_seqs, rec_words, edges);
   if (edges == EDGES_PARSED) return set_err(ctx, KMI_ERR_INVALID, "FASTQ edge tuples come in node form from the extract pass");
   KMI_DISPATCH(shape, extract_run_impl, ctx, cfg, bytes_dev, n_bytes, shape, file_offset, out_kmers_dev, out_ids_dev, out_quals_dev,
-               out_capacity, apply_strand, scan_done, n_tuples, n_seqs, rec_words, edges == EDGES_NODE);
+               out_capacity, apply_strand, scan_done, n_tuples, n_seqs, rec_words, edges == EDGES_NODE, read_scan);
 }
 
 // ---------------------------------------------------------------------------
@@ -1078,7 +1123,7 @@ kmi_status extract_run(kmi_ctx *ctx, const kmi_config *cfg, const uint8_t *bytes
 // where '@' is followed two lines later by '+' (a quality line may itself begin with '@').
 // ---------------------------------------------------------------------------
 // first record start at or after `pos` (n when there is none in the buffer)
-__device__ __forceinline__ uint64_t fastq_first_record_from(const uint8_t *__restrict__ bytes, uint64_t n, uint64_t pos, bool starts_file = true) {
+__host__ __device__ __forceinline__ uint64_t fastq_first_record_from(const uint8_t *__restrict__ bytes, uint64_t n, uint64_t pos, bool starts_file = true) {
   // starts_file = false: byte 0 of the buffer lies somewhere inside the file, so position 0 is examined like any other
   if (pos == 0 && starts_file) return 0;
   if (pos >= n) return n;
@@ -1100,6 +1145,28 @@ __device__ __forceinline__ uint64_t fastq_first_record_from(const uint8_t *__res
   else if (firsts[1] == '+' && firsts[3] == '@') c = starts[3];
   return c;
 }
+// end of the record-aligned batch of at most `batch` bytes that starts at record start `start` (fastq_batch_end): probes step back
+// from start + batch until a record start at or before it shows, then walk forward to the last such one
+__host__ __device__ __forceinline__ uint64_t fastq_batch_end_of(const uint8_t *__restrict__ bytes, uint64_t n, uint64_t start, uint64_t batch) {
+  if (n - start <= batch) return n;
+  const uint64_t lim = start + batch;
+  uint64_t c = n;
+  for (uint64_t back = 256;; back *= 2) {
+    const uint64_t p = (batch > back) ? lim - back : start + 1;
+    c = fastq_first_record_from(bytes, n, p, false);
+    if (c <= lim || p == start + 1) break;
+  }
+  if (c > lim) return c;   // one record larger than the batch: the batch grows to hold it
+  for (;;) {
+    const uint64_t nx = fastq_first_record_from(bytes, n, c + 1, false);
+    if (nx > lim || nx <= c) break;
+    c = nx;
+  }
+  return c;
+}
+__global__ void fastq_batch_end_kernel(const uint8_t *__restrict__ bytes, uint64_t n, uint64_t start, uint64_t batch, uint64_t *__restrict__ out) {
+  if (blockIdx.x == 0 && threadIdx.x == 0) *out = fastq_batch_end_of(bytes, n, start, batch);
+}
 __global__ void fastq_find_first_records_kernel(const uint8_t *__restrict__ bytes, uint64_t n, uint32_t n_parts, uint64_t *__restrict__ cuts) {
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r > n_parts) return;
@@ -1111,6 +1178,19 @@ __global__ void fastq_find_first_records_kernel(const uint8_t *__restrict__ byte
 __global__ void fastq_find_records_at_kernel(const uint8_t *__restrict__ bytes, uint64_t n, uint32_t n_pos, uint64_t *__restrict__ cuts, bool starts_file) {
   const uint32_t r = blockIdx.x * blockDim.x + threadIdx.x;
   if (r < n_pos) cuts[r] = fastq_first_record_from(bytes, n, cuts[r], starts_file);
+}
+
+uint64_t fastq_batch_end_host(const uint8_t *bytes, size_t n_bytes, uint64_t start, uint64_t batch) {
+  return fastq_batch_end_of(bytes, (uint64_t)n_bytes, start, batch);
+}
+kmi_status fastq_batch_end(kmi_ctx *ctx, const uint8_t *bytes_dev, size_t n_bytes, uint64_t start, uint64_t batch, uint64_t *end) {
+  if (n_bytes - start <= batch) { *end = n_bytes; return KMI_OK; }
+  hipLaunchKernelGGL(fastq_batch_end_kernel, dim3(1), dim3(64), 0, ctx->stream, bytes_dev, (uint64_t)n_bytes, start, batch, ctx->d_totals + 8);
+  KMI_HIP(ctx, hipGetLastError());
+  KMI_HIP(ctx, hipMemcpyAsync(ctx->h_totals + 8, ctx->d_totals + 8, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  *end = ctx->h_totals[8];
+  return KMI_OK;
 }
 
 }  // namespace kmi

@@ -4337,6 +4337,7 @@ static bool sk_rank_count(uint32_t p) { return p == 1u || p == 2u || p == 4u || 
 #include "kmi_unitig.h"
 #include "kmi_unitig_dist.h"
 #include "kmi_update.h"
+#include "kmi_lookup.h"
 
 struct kmi_comm;
 static kmi_status dist_state(kmi_index *idx, kmi_comm *comm, uint64_t *holders, uint64_t *owner_p, uint64_t *owner_any);
@@ -5934,6 +5935,56 @@ kmi_status kmi_index_update_pairs_host(kmi_index *idx, const uint64_t *records, 
   KMI_TRY(ws_get(ctx, WS_INPUT2, bytes + 64, &dr));
   KMI_HIP(ctx, hipMemcpyAsync(dr, records, bytes, hipMemcpyHostToDevice, ctx->stream));
   return index_update_pairs(idx, (uint64_t *)dr, n, (int)op, n_updated);
+}
+
+// ---- queries in the caller's order (kmi_lookup.h)
+kmi_status kmi_index_lookup_dev(kmi_index *idx, const uint64_t *queries_dev, size_t nq, uint32_t *counts_dev) {
+  if (!idx) return KMI_ERR_INVALID;
+  kmi_ctx *ctx = idx->ctx;
+  if (idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "lookup() is a member of the count index");
+  if (nq == 0) return KMI_OK;
+  if (!queries_dev || !counts_dev) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
+  KMI_HIP(ctx, hipSetDevice(ctx->device));
+  return index_lookup(idx, queries_dev, nq, counts_dev);
+}
+
+kmi_status kmi_index_lookup_host(kmi_index *idx, const uint64_t *queries, size_t nq, uint32_t *counts) {
+  if (!idx) return KMI_ERR_INVALID;
+  kmi_ctx *ctx = idx->ctx;
+  if (idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "lookup() is a member of the count index");
+  if (nq == 0) return KMI_OK;
+  if (!queries || !counts) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
+  KMI_HIP(ctx, hipSetDevice(ctx->device));
+  void *dq, *dc;
+  KMI_TRY(ws_get(ctx, WS_INPUT, nq * idx->shape.n_words * sizeof(uint64_t), &dq));
+  KMI_TRY(ws_get(ctx, WS_OUTPUT, nq * sizeof(uint32_t), &dc));
+  KMI_HIP(ctx, hipMemcpyAsync(dq, queries, nq * idx->shape.n_words * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+  KMI_TRY(index_lookup(idx, (const uint64_t *)dq, nq, (uint32_t *)dc));
+  KMI_HIP(ctx, hipMemcpyAsync(counts, dc, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return KMI_OK;
+}
+
+static kmi_status profile_reads_entry(kmi_index *idx, const uint8_t *bytes, size_t n_bytes, bool on_device, uint32_t solid_threshold,
+                                      kmi_read_profile *out, size_t capacity, uint64_t *n_reads) {
+  if (!idx || !n_reads) return KMI_ERR_INVALID;
+  kmi_ctx *ctx = idx->ctx;
+  *n_reads = 0;
+  if (idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "profile_reads() is a member of the count index");
+  if (idx->cfg.seq_format != KMI_FMT_FASTQ) return set_err(ctx, KMI_ERR_INVALID, "profile_reads() reads FASTQ");
+  if (solid_threshold == 0) return set_err(ctx, KMI_ERR_INVALID, "solid_threshold is at least 1");
+  if (n_bytes == 0) return KMI_OK;
+  if (!bytes || (!out && capacity)) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
+  KMI_HIP(ctx, hipSetDevice(ctx->device));
+  return index_profile_reads(idx, bytes, n_bytes, on_device, solid_threshold, out, capacity, n_reads);
+}
+kmi_status kmi_index_profile_reads_dev(kmi_index *idx, const uint8_t *bytes_dev, size_t n_bytes, uint32_t solid_threshold, kmi_read_profile *out_dev,
+                                       size_t capacity, uint64_t *n_reads) {
+  return profile_reads_entry(idx, bytes_dev, n_bytes, true, solid_threshold, out_dev, capacity, n_reads);
+}
+kmi_status kmi_index_profile_reads_host(kmi_index *idx, const uint8_t *bytes, size_t n_bytes, uint32_t solid_threshold, kmi_read_profile *out,
+                                        size_t capacity, uint64_t *n_reads) {
+  return profile_reads_entry(idx, bytes, n_bytes, false, solid_threshold, out, capacity, n_reads);
 }
 
 }  // extern "C"

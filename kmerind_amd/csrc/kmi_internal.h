@@ -64,6 +64,8 @@ enum WsSlot {
   WS_UNI_STAGE,       // ... staged 16-byte records of every state before they are grouped by rank; the link requests
   WS_UNI_END,         // ... cycle candidates, then the end k-mer and end occurrences of every state
   WS_UNI_CNT,         // ... records per destination rank, cursors, device scalars
+  WS_LOOKUP_RECS,     // positional lookup / read profile (kmi_lookup.h): (key words, tag) records of the queries or of a batch's k-mers
+  WS_LOOKUP_CNT,      // ... the looked-up count of every k-mer of a batch, in file order
   WS_NUM_SLOTS
 };
 
@@ -135,6 +137,9 @@ struct kmi_ctx {
   int sk_dbg = 0;                // KMI_SK_DBG=7 (test knob): the super-k-mer front end reports a capacity as exceeded
   bool fa_part_set = false;      // kmi_ctx_set_fasta_partition
   kmi_fasta_partition fa_part{};
+  uint32_t lookup_cap = 0;       // home slots of bucket_lookup_kernel's table (KMI_LOOKUP_CAP: tests reach the multi-pass code with a small index); 0: the table's own
+  size_t profile_batch = (size_t)256 << 20;   // input bytes of a batch of kmi_index_profile_reads_* (KMI_PROFILE_BATCH)
+  uint64_t lookup_npass = 0;     // the largest pass count a bucket used in the last lookup / profile (kmi_ctx_debug_counter 8)
   int fa_left_carry = -1;        // de Bruijn tuples of a FASTA block (kmi_dbg_build_fasta_range_dist_host): the raw byte of the sequence
                                  // character before the block's first one, the in-edge of its first window; -1: none
 };
@@ -309,11 +314,18 @@ kmi_status extract_count(kmi_ctx *ctx, const kmi_config *cfg, const uint8_t *byt
 kmi_status extract_run(kmi_ctx *ctx, const kmi_config *cfg, const uint8_t *bytes_dev, size_t n_bytes,
                        uint64_t file_offset, uint64_t *out_kmers_dev, uint64_t *out_ids_dev, size_t out_capacity,
                        bool apply_strand, bool scan_done, uint64_t *n_tuples, uint64_t *n_seqs, float *out_quals_dev = nullptr,
-                       uint32_t rec_words = 0, uint32_t edges = EDGES_NONE);
+                       uint32_t rec_words = 0, uint32_t edges = EDGES_NONE, struct ReadScan *read_scan = nullptr);
 kmi_status upload_quality_lut(kmi_ctx *ctx);
 
 // tile scan of a FASTQ partition; the packed arrays and per-tile line bases stay in the workspace
 struct ReadDesc { uint64_t seq_pos, out_off; };   // slot = sequence index of the read; out_off = ~0: the read has no k-mer
+// what extract_run leaves for a per-read pass over its tuples (FASTQ, records with ids): a descriptor for EVERY record of the buffer
+// (seq_pos = ~0: the record has no sequence line; out_off = ~0: no k-mer), the EOL bitmap of the scan and the buffer's line count
+struct ReadScan { const ReadDesc *reads; const uint32_t *eolw; uint64_t n_eol_words, n_lines; };
+// end of the record-aligned batch that starts at record start `start`: the last record start in (start, start + batch], or the
+// first one behind it when one record is larger than the batch; n_bytes when the rest of the buffer fits (bytes on the device / host)
+kmi_status fastq_batch_end(kmi_ctx *ctx, const uint8_t *bytes_dev, size_t n_bytes, uint64_t start, uint64_t batch, uint64_t *end);
+uint64_t fastq_batch_end_host(const uint8_t *bytes, size_t n_bytes, uint64_t start, uint64_t batch);
 struct FastqScan {
   uint64_t n_tiles, n_tuples, n_seqs, n_bytes, n_cover;
   const uint32_t *line_base;
