@@ -245,6 +245,8 @@ kmi_status kmi_ctx_create(int device, int rank, int nranks, void *stream, kmi_ct
   if (const char *hm = getenv("KMI_HOST_OVERLAP_MIN")) ctx->host_overlap_min = strtoull(hm, nullptr, 10);
   if (const char *fc = getenv("KMI_FEED_MIN_CHUNK")) { ctx->feed_min_chunk = strtoull(fc, nullptr, 10); if (ctx->feed_min_chunk < 4096) ctx->feed_min_chunk = 4096; }
   if (const char *mr = getenv("KMI_FRONT_MIN_RANGE")) { ctx->front_min_range = strtoull(mr, nullptr, 10); ctx->front_min_range = (ctx->front_min_range + 4095) / 4096 * 4096; if (!ctx->front_min_range) ctx->front_min_range = 4096; }
+  if (const char *rw = getenv("KMI_FRONT_RANGES_PER_WAVE")) { ctx->front_ranges_per_wave = (uint32_t)strtoul(rw, nullptr, 10); if (ctx->front_ranges_per_wave < 1) ctx->front_ranges_per_wave = 1; if (ctx->front_ranges_per_wave > 16) ctx->front_ranges_per_wave = 16; }
+  if (const char *mw = getenv("KMI_FRONT_MAX_WAVES")) ctx->front_max_waves = (uint32_t)strtoul(mw, nullptr, 10);
   if (const char *sm = getenv("KMI_SPARSE_MIN")) ctx->sparse_min = strtoull(sm, nullptr, 10);
   if (const char *fd = getenv("KMI_FORCE_DIST")) ctx->force_dist = atoi(fd) != 0;
   if (const char *lc = getenv("KMI_LOOKUP_CAP")) { ctx->lookup_cap = (uint32_t)strtoul(lc, nullptr, 10); if (ctx->lookup_cap < 64) ctx->lookup_cap = 64; }   // (the upper bound is the table's: kmi_lookup.h)

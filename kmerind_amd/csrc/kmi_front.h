@@ -7,7 +7,8 @@
 // build's 9 ms issuing instructions on bytes that never become k-mers: every byte was classified into a 2-bit code although 52 %
 // of a record are header, '+' and quality, and the line bookkeeping went through three passes over bitmaps.
 //
-// Here every WAVEFRONT owns a byte range and runs on its own (no workgroup barrier in the kernel):
+// Here every WAVEFRONT works a byte range at a time, on its own (no workgroup barrier in the kernel; a large input has four ranges
+// per resident wavefront, and a wavefront takes its next one from a queue word):
 //   produce   64 lanes x 64 bytes: EOL bits only (SWAR), line starts / ends ranked with one DPP scan, their positions into two
 //             small rings in LDS; complete lines get their role from the line index; sequence lines become runs of windows
 //   consume   as soon as 64 runs wait: one lane per run loads the read's own bytes, packs THEM (and nothing else) into 2-bit
@@ -20,6 +21,7 @@
 // chain that does not close, a capacity exceeded -- raises ONE flag and the caller runs the general path (fastq_scan + list +
 // minimizer), which also words the error. So this path is exact on well-formed input and silent on everything else.
 #pragma once
+#include "kmi_front_bytes.h"   // eol_flags, pack_codes4: the dword functions, also run on the host (tests/cpu)
 
 namespace kmi {
 
@@ -42,13 +44,6 @@ template <int W> struct FrCfg {
   static constexpr int NR = (ND + 3) / 4;               // packed words that can hold a base: 10, 7, 6, 4
 };
 
-// 0x80 in every byte of w that is '\n' or '\r' (exact): x = w ^ 0x0A.. turns them into 0x00 / 0x07; a byte is one of the two iff
-// its high five bits are clear and its low three are 000 or 111, i.e. iff (x & 0xF8) | (((x & 7) + 1) & 6) is zero
-__device__ __forceinline__ uint32_t eol_flags(uint32_t w) {
-  const uint32_t x = w ^ 0x0A0A0A0Au;
-  const uint32_t z = ((x & 0x07070707u) + 0x01010101u) & 0x06060606u;
-  return zero_bytes((x & 0xF8F8F8F8u) | z);
-}
 // four bases -> four complement codes in the low byte; anything but A C G T (either case) counts as A, like DNA::FROM_ASCII
 __device__ __forceinline__ uint32_t pack_dna4(uint32_t w, uint32_t *ok_out = nullptr) {
   const uint32_t x = w & 0xDFDFDFDFu;                          // fold case
@@ -70,13 +65,23 @@ __device__ __forceinline__ uint32_t dna4_ok(uint32_t w) {
   return zero_bytes(x ^ byte_perm(0u, 0x47544341u, idx));
 }
 
+#if defined(KMI_FR_TIMING) && !defined(KMI_FR_LEAVE)
+#define KMI_FR_LEAVE
+#endif
+#ifdef KMI_FR_LEAVE
+// (-DKMI_FR_LEAVE builds; the phase clocks of -DKMI_FR_TIMING cost registers, this does not) when every wavefront of the last launch
+// entered and left the kernel: two wall-clock words per wavefront
+constexpr uint32_t kFrTimingWaves = 16384;
+__device__ unsigned long long g_fr_wave_clock[2 * kFrTimingWaves];
+#endif
+
 template <int W, bool EDGES = false>
 __global__ __launch_bounds__(kFrThreads) void sk_front_kernel(const uint8_t *__restrict__ bytes, uint64_t n_bytes, uint64_t range_bytes, uint32_t n_ranges,
                                                              uint32_t k, bool rna, uint32_t run_cap, uint32_t item_cap, uint32_t ranges_per_group,
                                                              FrRange *__restrict__ info, uint32_t *__restrict__ run_items, uint32_t *__restrict__ rows,
                                                              uint32_t *__restrict__ items, uint32_t *__restrict__ wg_hist,
                                                              unsigned long long *__restrict__ n_windows, uint32_t *__restrict__ flags,
-                                                             uint32_t r_first = 0u, uint32_t r_end = 0xffffffffu) {
+                                                             uint32_t r_first = 0u, uint32_t r_end = 0xffffffffu, uint32_t *__restrict__ queue = nullptr) {
   constexpr bool edges = EDGES;   // (a kernel of its own: the checks it adds cost the build that does not need them a quarter of this kernel's time)
   // EDGES (the de Bruijn node build, kmi_debruijn.h): a record also carries the base before its first and the base behind its last
   // k-mer (two 3-bit codes in the place of its last three bases: super-k-mers are cut three windows earlier), which the scatter pass
@@ -84,6 +89,11 @@ __global__ __launch_bounds__(kFrThreads) void sk_front_kernel(const uint8_t *__r
   // (an N is an A inside a k-mer but its own DNA16 code as a neighbour, edge_iterator.hpp:163-177: the general build decides then)
   // r_first / r_end: this launch takes the ranges [r_first, min(r_end, n_ranges)) -- a build from host memory launches the kernel
   // once per arrived chunk of the input, for the ranges whose bytes (and the bytes a range may scan behind its end) are there
+  // queue (zero at launch, one launch per zeroing): there are more ranges than wavefronts, and a wavefront that has worked its own
+  // range (the one with its number) takes its next one from this counter -- the oldest wavefront of a SIMD is issued first and gets
+  // through its bytes well before the youngest, and with equal static shares the SIMD then runs on two wavefronts, then on one.
+  // The counter only hands out numbers: no wavefront waits for another. Without a queue (the launches of a host-fed build share
+  // the flags) a wavefront takes every n_waves-th range.
   if (r_end > n_ranges) r_end = n_ranges;
   using F = FrCfg<W>;
   constexpr int CAP = kSkListCap;
@@ -100,18 +110,26 @@ __global__ __launch_bounds__(kFrThreads) void sk_front_kernel(const uint8_t *__r
   const uint32_t nmax = sk_nmax_of(k) - (edges ? kSkEdgeWindows : 0u);
   const uint32_t seg = (uint32_t)F::SEG;
   const uint32_t n_waves = gridDim.x * (uint32_t)kFrWaves;
+#ifdef KMI_FR_LEAVE
+  const unsigned long long t_enter = wall_clock64();
+#endif
 #ifdef KMI_FR_TIMING
   unsigned long long acc[8] = {0, 0, 0, 0, 0, 0, 0, 0}, tq = clock64();
 #define FQ_MARK(i) { const unsigned long long now_ = clock64(); acc[i] += now_ - tq; tq = now_; }
 #else
 #define FQ_MARK(i)
 #endif
-  for (uint32_t r = r_first + blockIdx.x * (uint32_t)kFrWaves + wv; r < r_end; r += n_waves) {   // (uniform per wavefront)
+  for (uint32_t r = r_first + blockIdx.x * (uint32_t)kFrWaves + wv; r < r_end;) {   // (uniform per wavefront)
     const uint64_t B = (uint64_t)r * range_bytes;
     const uint32_t len = (uint32_t)((n_bytes - B < range_bytes) ? (n_bytes - B) : range_bytes);
     for (uint32_t i = lane; i < (uint32_t)kNumCoarse; i += kWave) hist[i] = 0;
     uint32_t why = 0; bool bail = false;                               // this range gives up: the caller takes the general path
+    // the range after this one: asked for now, one range ahead (lane 0's atomic; its answer comes in with the byte before the range,
+    // which is waited for anyway, and stays in a scalar register)
+    uint32_t q_next = 0;
+    if (queue && lane == 0) q_next = atomicAdd(queue, 1u);
     uint32_t carry = (B == 0) ? 1u : (is_eol((uint32_t)__builtin_amdgcn_readfirstlane((int)bytes[B - 1])) ? 1u : 0u);   // EOL status of the byte before the next step
+    const uint32_t r_next = queue ? r_first + n_waves + (uint32_t)__builtin_amdgcn_readfirstlane((int)q_next) : r + n_waves;
     const uint32_t eoff = carry ? 0u : 1u;           // the range starts inside a line: that line's end is not ours
     uint32_t n_starts = 0, n_ends = 0, n_owned = 0, done = 0, l0 = (r == 0) ? 0u : INF;
     if (r == 0 && __builtin_amdgcn_readfirstlane((int)bytes[0]) != (int)'@') { why |= 2u; bail = true; }      // (get_next_record refuses a partition that does not begin with '@')
@@ -273,36 +291,69 @@ __global__ __launch_bounds__(kFrThreads) void sk_front_kernel(const uint8_t *__r
 #pragma unroll
       for (int i = 0; i < 16; ++i) rw[i] = 0;
       uint32_t other = 0;   // edges: 0x80 per byte of the run that is none of A C G T
-      if (mine) {
-        if (g0 + 16ull * F::NR <= n_bytes) {
+      // today's exact routine: every byte gets its validity mask, and a byte that is none of A C G T the code of A
+      auto pack_exact = [&]() {
 #pragma unroll
-          for (int q = 0; q < F::NR; ++q) {
-            FrU4 v = *reinterpret_cast<const FrU4 *>(bytes + g0 + 16 * q);   // (a read starts at any byte: unaligned 16-byte loads)
-            if (rna) { v.x = swap_tu_dword(v.x); v.y = swap_tu_dword(v.y); v.z = swap_tu_dword(v.z); v.w = swap_tu_dword(v.w); }
-            uint32_t okd[4];
-            rw[q] = pack_dna4(v.x, &okd[0]) | (pack_dna4(v.y, &okd[1]) << 8) | (pack_dna4(v.z, &okd[2]) << 16) | (pack_dna4(v.w, &okd[3]) << 24);
-            if (edges) {   // uniform: every byte of the run's nb bases has to be one of A C G T
-              const uint32_t nbits = 8u * (L + k - 1u);
+        for (int q = 0; q < F::NR; ++q) {
+          FrU4 v = *reinterpret_cast<const FrU4 *>(bytes + g0 + 16 * q);   // (a read starts at any byte: unaligned 16-byte loads)
+          if (rna) { v.x = swap_tu_dword(v.x); v.y = swap_tu_dword(v.y); v.z = swap_tu_dword(v.z); v.w = swap_tu_dword(v.w); }
+          uint32_t okd[4];
+          rw[q] = pack_dna4(v.x, &okd[0]) | (pack_dna4(v.y, &okd[1]) << 8) | (pack_dna4(v.z, &okd[2]) << 16) | (pack_dna4(v.w, &okd[3]) << 24);
+          if (edges) {   // uniform: every byte of the run's nb bases has to be one of A C G T
+            const uint32_t nbits = 8u * (L + k - 1u);
 #pragma unroll
-              for (int e = 0; e < 4; ++e) {
-                const uint32_t at = 8u * (16u * (uint32_t)q + 4u * (uint32_t)e);   // first bit of this dword in the run
-                const uint32_t vm = nbits >= at + 32u ? 0x80808080u : (nbits <= at ? 0u : (0x80808080u & ((1u << (nbits - at)) - 1u)));
-                other |= ~okd[e] & vm;
-              }
+            for (int e = 0; e < 4; ++e) {
+              const uint32_t at = 8u * (16u * (uint32_t)q + 4u * (uint32_t)e);   // first bit of this dword in the run
+              const uint32_t vm = nbits >= at + 32u ? 0x80808080u : (nbits <= at ? 0u : (0x80808080u & ((1u << (nbits - at)) - 1u)));
+              other |= ~okd[e] & vm;
             }
           }
-        } else {   // the last reads of the buffer: byte by byte, nothing read past the end
+        }
+      };
+      constexpr bool fast_pack = !edges;   // (the edge records need the per-byte mask anyway)
+      const bool whole = mine && g0 + 16ull * F::NR <= n_bytes;   // the run's sixteen-byte loads stay inside the buffer
+      if (fast_pack) {
+        // A read is A C G T and nothing else, nearly always: the codes come from a table lookup and a dot product per dword
+        // (pack_codes4), with no validity select. Whether that was right is found out on the side: the differences between the bytes
+        // and the letters their codes stand for are OR-ed together over the sixteen-byte groups that lie wholly inside the run's
+        // nb = L + k - 1 bases, and the one group that holds the run's last 1 .. 15 bases is looked at again under a byte mask (what
+        // lies behind a run's end -- EOLs, '+', quality characters -- must not raise the flag; in the row those bytes leave codes that
+        // nothing reads, as before). If any lane of the wavefront saw another byte, the wavefront packs this batch with the exact
+        // routine: the rows are today's, bit for bit, wherever a byte is not a base.
+        uint32_t bad = 0;
+        if (whole) {
           const uint32_t nb = L + k - 1u;
-#pragma unroll 1
-          for (uint32_t i = 0; i < nb; ++i) {
-            uint32_t c = bytes[g0 + i];
-            if (rna) c = swap_tu_dword(c) & 0xffu;
-            const uint32_t code = pack_dna4(c | 0x0A0A0A00u) & 3u;
-            if (edges) other |= ~dna4_ok(c | 0x41414100u) & 0x80u;
-            const uint32_t wi = i >> 4, sh = (i & 15u) * 2u;
 #pragma unroll
-            for (int q = 0; q < F::NR; ++q) rw[q] |= (wi == (uint32_t)q) ? (code << sh) : 0u;
+          for (int q = 0; q < F::NR; ++q) {
+            FrU4 v = *reinterpret_cast<const FrU4 *>(bytes + g0 + 16 * q);
+            if (rna) { v.x = swap_tu_dword(v.x); v.y = swap_tu_dword(v.y); v.z = swap_tu_dword(v.z); v.w = swap_tu_dword(v.w); }
+            uint32_t d = 0;
+            const uint32_t c0 = pack_codes4(v.x, d), c1 = pack_codes4(v.y, d), c2 = pack_codes4(v.z, d), c3 = pack_codes4(v.w, d);
+            rw[q] = c0 | (c1 << 8) | (c2 << 16) | (c3 << 24);
+            bad |= (16u * (uint32_t)(q + 1) <= nb) ? d : 0u;
           }
+          const uint32_t rem = nb & 15u, qt = nb >> 4;   // (rem != 0: qt < NR, sixteen NR bytes hold the longest run)
+          if (rem) {
+            FrU4 v = *reinterpret_cast<const FrU4 *>(bytes + g0 + 16u * qt);
+            if (rna) { v.x = swap_tu_dword(v.x); v.y = swap_tu_dword(v.y); v.z = swap_tu_dword(v.z); v.w = swap_tu_dword(v.w); }
+            bad |= dna4_other_in_first(v.x, rem) | dna4_other_in_first(v.y, rem > 4u ? rem - 4u : 0u) |
+                   dna4_other_in_first(v.z, rem > 8u ? rem - 8u : 0u) | dna4_other_in_first(v.w, rem > 12u ? rem - 12u : 0u);
+          }
+          bad &= 0xDFDFDFDFu;
+        }
+        if (__any(bad != 0u)) { if (whole) pack_exact(); }
+      } else if (whole) pack_exact();
+      if (mine && !whole) {   // the last reads of the buffer: byte by byte, nothing read past the end
+        const uint32_t nb = L + k - 1u;
+#pragma unroll 1
+        for (uint32_t i = 0; i < nb; ++i) {
+          uint32_t c = bytes[g0 + i];
+          if (rna) c = swap_tu_dword(c) & 0xffu;
+          const uint32_t code = pack_dna4(c | 0x0A0A0A00u) & 3u;
+          if (edges) other |= ~dna4_ok(c | 0x41414100u) & 0x80u;
+          const uint32_t wi = i >> 4, sh = (i & 15u) * 2u;
+#pragma unroll
+          for (int q = 0; q < F::NR; ++q) rw[q] |= (wi == (uint32_t)q) ? (code << sh) : 0u;
         }
       }
       if (edges) {   // uniform
@@ -320,13 +371,16 @@ __global__ __launch_bounds__(kFrThreads) void sk_front_kernel(const uint8_t *__r
         if (__any(other != 0u)) { why |= 1024u; bail = true; break; }
       }
       FQ_MARK(3)
-      // the row leaves now (the walk below consumes its registers): three 16-byte stores per lane, consecutive rows
+      // the row leaves now (the walk below consumes its registers): three stores per lane, consecutive rows. Words 10 and 11 hold no
+      // base; only the edge records use word 11 (the scatter pass reads nothing of them otherwise), and two registers kept at zero
+      // through the whole kernel for them were two registers too many.
       if (mine) {
         const uint64_t ri = (uint64_t)r * run_cap + run_count + lane;
         uint4 *rp = reinterpret_cast<uint4 *>(rows + ri * kFrRowDw);
         rp[0] = make_uint4(rw[0], rw[1], rw[2], rw[3]);
         rp[1] = make_uint4(rw[4], rw[5], rw[6], rw[7]);
-        rp[2] = make_uint4(rw[8], rw[9], rw[10], rw[11]);
+        if (edges) rp[2] = make_uint4(rw[8], rw[9], rw[10], rw[11]);
+        else *reinterpret_cast<uint2 *>(rp + 2) = make_uint2(rw[8], rw[9]);
       }
       // ---- the walk (sk_minimizer_kernel's). The row is kept ALIGNED to the block being walked: after the first m - 1 bases are
       // shifted out once, the W codes of a block are the low 2 W bits of rw[0..1], and the row moves down by W bases per block
@@ -497,9 +551,16 @@ __global__ __launch_bounds__(kFrThreads) void sk_front_kernel(const uint8_t *__r
     }
     wave_sync();
     FQ_MARK(7)
+    r = r_next;
   }
 #ifdef KMI_FR_TIMING
   if (lane == 0) for (int i = 0; i < 8; ++i) atomicAdd(&reinterpret_cast<unsigned long long *>(flags + 48)[i], acc[i]);
+#endif
+#ifdef KMI_FR_LEAVE
+  if (lane == 0 && blockIdx.x * (uint32_t)kFrWaves + wv < kFrTimingWaves) {
+    g_fr_wave_clock[2u * (blockIdx.x * (uint32_t)kFrWaves + wv)] = t_enter;
+    g_fr_wave_clock[2u * (blockIdx.x * (uint32_t)kFrWaves + wv) + 1u] = wall_clock64();
+  }
 #endif
 }
 
@@ -561,7 +622,14 @@ __global__ __launch_bounds__(kFrScThreads, 2) void sk_scatter_rows_kernel(const 
     uint32_t ri = 0, q = 0;
     uint64_t run = 0;
     if (G < total_runs) {
-      for (uint32_t i = 1; i < nr; ++i) q += (G >= s_pre[i]) ? 1u : 0u;
+      // the last range whose runs begin at or before G (the prefix only grows): a binary search, seven probes for up to
+      // kFrMaxGroupRanges ranges -- a group holds a few dozen since the front end hands its ranges out from a queue
+      static_assert(kFrMaxGroupRanges <= 128u, "seven probes");
+#pragma unroll
+      for (uint32_t step = 64u; step; step >>= 1) {
+        const uint32_t t = q + step;
+        if (t < nr && G >= s_pre[t]) q = t;
+      }
       run = (uint64_t)(r_first + q) * run_cap + (G - s_pre[q]);
       ri = run_items[run];
     }
@@ -671,19 +739,24 @@ __global__ __launch_bounds__(1024) void sk_front_verify_kernel(const FrRange *__
   __shared__ uint32_t s_bad;
   if (threadIdx.x == 0) s_bad = 0;
   lds_barrier();
-  uint64_t carry = 0, runs = 0, its = 0;
-  for (uint32_t r0 = 0; r0 < n_ranges; r0 += 1024) {
-    const uint32_t r = r0 + threadIdx.x;
-    FrRange fr; fr.l0 = kFrNone; fr.n_lines = 0; fr.n_runs = 0; fr.n_items = 0;
-    if (r < n_ranges) fr = info[r];
-    uint64_t tot;
-    const uint64_t before = carry + block_exclusive_scan<uint64_t>((uint64_t)fr.n_lines, s_scan, &tot);
-    if (fr.l0 != kFrNone && fr.n_lines && ((uint32_t)before & 3u) != fr.l0) s_bad = 1;
-    carry += tot;
-    uint64_t t2;
-    (void)block_exclusive_scan<uint64_t>((uint64_t)fr.n_runs, s_scan, &t2); runs += t2;
-    (void)block_exclusive_scan<uint64_t>((uint64_t)fr.n_items, s_scan, &t2); its += t2;
+  // every thread takes a run of consecutive ranges: their sums first, one scan over the threads, then the chain through its own
+  // ranges (a scan per 1024 ranges was 0.1 ms of a single workgroup once the front end cut the input into 12 k ranges and more)
+  const uint32_t per = (n_ranges + 1023u) / 1024u;
+  const uint32_t r_lo = threadIdx.x * per < n_ranges ? threadIdx.x * per : n_ranges, r_hi = r_lo + per < n_ranges ? r_lo + per : n_ranges;
+  uint64_t my_lines = 0, my_runs = 0, my_its = 0;
+  for (uint32_t r = r_lo; r < r_hi; ++r) {
+    const FrRange fr = info[r];
+    my_lines += fr.n_lines; my_runs += fr.n_runs; my_its += fr.n_items;
   }
+  uint64_t carry = 0, runs = 0, its = 0;
+  uint64_t before = block_exclusive_scan<uint64_t>(my_lines, s_scan, &carry);
+  for (uint32_t r = r_lo; r < r_hi; ++r) {
+    const FrRange fr = info[r];
+    if (fr.l0 != kFrNone && fr.n_lines && ((uint32_t)before & 3u) != fr.l0) s_bad = 1;
+    before += fr.n_lines;
+  }
+  (void)block_exclusive_scan<uint64_t>(my_runs, s_scan, &runs);
+  (void)block_exclusive_scan<uint64_t>(my_its, s_scan, &its);
   lds_barrier();
   if (threadIdx.x == 0) {
     totals[0] = carry; totals[1] = runs; totals[2] = its;

@@ -3009,9 +3009,16 @@ static kmi_status sk_front_fast(kmi_ctx *ctx, const kmi_config *cfg, const KShap
     if (hipOccupancyMaxActiveBlocksPerMultiprocessor(&per_cu, sk_front_kernel<19, false>, kFrThreads, 0) != hipSuccess || per_cu <= 0) per_cu = 2;
     ctx->front_waves = (uint32_t)per_cu * (ctx->n_cus ? ctx->n_cus : 256u) * (uint32_t)kFrWaves;
   }
+  // Several ranges per wavefront: the kernel is launched with the resident wavefronts and they take their ranges from a queue,
+  // so a SIMD keeps its three wavefronts busy until the input runs out (with one range each the oldest wavefront of a SIMD, which
+  // is issued first, left long before the youngest). A range pays for its start (the inferred line index) and its end (it scans
+  // on in whole steps until two lines behind its last byte are complete), and its last batch of runs is walked however few of its 64
+  // lanes it fills: four per wavefront, 256 KB on 3 GB, measured best of 2 .. 6, 8 and 16 (profiles/r08_a_ab_front_queue.txt).
   // (fed from host memory: sixteen times the ranges -- what runs after the last byte has arrived is one range per wavefront slot,
-  // and a range is worked through by one wavefront from end to end: 0.35 ms for 256 KB)
-  uint64_t range_bytes = (n_bytes + ctx->front_waves * (fed ? 16u : 1u) - 1) / (ctx->front_waves * (fed ? 16u : 1u));
+  // and a range is worked through by one wavefront from end to end: 0.35 ms for 256 KB -- and no queue: the launches of the
+  // chunks share the flags, and a counter would hand one launch's numbers to another)
+  const uint32_t per_wave = fed ? 16u : ctx->front_ranges_per_wave;
+  uint64_t range_bytes = (n_bytes + (uint64_t)ctx->front_waves * per_wave - 1) / ((uint64_t)ctx->front_waves * per_wave);
   range_bytes = (range_bytes + kFrStep - 1) / kFrStep * kFrStep;
   if (range_bytes < ctx->front_min_range) range_bytes = ctx->front_min_range;
   if (range_bytes > (8ull << 20)) range_bytes = 8ull << 20;
@@ -3029,18 +3036,26 @@ static kmi_status sk_front_fast(kmi_ctx *ctx, const kmi_config *cfg, const KShap
   KMI_TRY(ws_get(ctx, WS_WGHIST, sizeof(uint32_t) * kPartGroups * kNumCoarse, &p)); uint32_t *wg_hist = (uint32_t *)p;
   KMI_TRY(ws_get(ctx, WS_CURSOR, sizeof(uint64_t) * kPartGroups * kNumCoarse, &p)); uint64_t *wg_off = (uint64_t *)p;
   KMI_TRY(ws_get(ctx, WS_MISC, sizeof(uint64_t) * kNumCoarse * 3, &p)); uint64_t *cnt = (uint64_t *)p, *base = cnt + kNumCoarse;
-  // (flags 0 .. 15, the k-mer total and the group histograms, in one launch)
+  // (flags 0 .. 15 -- word 12 is the front kernel's range queue --, the k-mer total and the group histograms, in one launch)
   hipLaunchKernelGGL(sk_zero_kernel, dim3(128), dim3(1024), 0, ctx->stream, wg_hist, (uint32_t)(kPartGroups * kNumCoarse),
                      reinterpret_cast<uint32_t *>(ctx->d_totals + 6), 2u, (uint32_t *)nullptr, 0u, ctx->d_flags, 0u, 16u, 0u, 0u);
+  uint32_t front_launched_waves = 0;   // (timing builds report on them)
+  (void)front_launched_waves;
   if (!fed) {
     ProfScope ps(ctx, "sk_front", n_bytes);
-    const uint32_t wgs = (n_ranges + kFrWaves - 1) / kFrWaves;
+    // as many wavefronts as are resident (or as the context allows), never more than there are ranges; the rest of the ranges
+    // go through the queue word, which the launch above has zeroed
+    uint32_t waves = ctx->front_max_waves ? std::min(ctx->front_waves, ctx->front_max_waves) : ctx->front_waves;
+    waves = std::max<uint32_t>((uint32_t)kFrWaves, waves / (uint32_t)kFrWaves * (uint32_t)kFrWaves);
+    const uint32_t wgs = std::min((n_ranges + kFrWaves - 1) / kFrWaves, waves / (uint32_t)kFrWaves);
+    front_launched_waves = wgs * (uint32_t)kFrWaves;
+    uint32_t *const queue = ctx->d_flags + 12;
     if (ctx->edge_records)
       hipLaunchKernelGGL((sk_front_kernel<W, true>), dim3(wgs), dim3(kFrThreads), 0, ctx->stream, bytes_dev, (uint64_t)n_bytes, range_bytes, n_ranges, k, is_rna(cfg),
-                         run_cap, item_cap, rpg, info, run_items, rows, items, wg_hist, (unsigned long long *)(ctx->d_totals + 6), ctx->d_flags, 0u, 0xffffffffu);
+                         run_cap, item_cap, rpg, info, run_items, rows, items, wg_hist, (unsigned long long *)(ctx->d_totals + 6), ctx->d_flags, 0u, 0xffffffffu, queue);
     else
       hipLaunchKernelGGL((sk_front_kernel<W, false>), dim3(wgs), dim3(kFrThreads), 0, ctx->stream, bytes_dev, (uint64_t)n_bytes, range_bytes, n_ranges, k, is_rna(cfg),
-                         run_cap, item_cap, rpg, info, run_items, rows, items, wg_hist, (unsigned long long *)(ctx->d_totals + 6), ctx->d_flags, 0u, 0xffffffffu);
+                         run_cap, item_cap, rpg, info, run_items, rows, items, wg_hist, (unsigned long long *)(ctx->d_totals + 6), ctx->d_flags, 0u, 0xffffffffu, queue);
   } else {
     // The input is still in host memory: its copy goes out in chunks on a stream of its own, all of them queued now, and behind every
     // chunk the front end takes the ranges whose bytes have arrived -- a range reads up to kFrOverrun + three steps behind its own end
@@ -3089,10 +3104,10 @@ static kmi_status sk_front_fast(kmi_ctx *ctx, const kmi_config *cfg, const KShap
       const uint32_t wgs = (r_end - r_done + kFrWaves - 1) / kFrWaves;
       if (ctx->edge_records)
         hipLaunchKernelGGL((sk_front_kernel<W, true>), dim3(wgs), dim3(kFrThreads), 0, ctx->stream, bytes_dev, (uint64_t)n_bytes, range_bytes, n_ranges, k, is_rna(cfg),
-                           run_cap, item_cap, rpg, info, run_items, rows, items, wg_hist, (unsigned long long *)(ctx->d_totals + 6), ctx->d_flags, r_done, r_end);
+                           run_cap, item_cap, rpg, info, run_items, rows, items, wg_hist, (unsigned long long *)(ctx->d_totals + 6), ctx->d_flags, r_done, r_end, (uint32_t *)nullptr);
       else
         hipLaunchKernelGGL((sk_front_kernel<W, false>), dim3(wgs), dim3(kFrThreads), 0, ctx->stream, bytes_dev, (uint64_t)n_bytes, range_bytes, n_ranges, k, is_rna(cfg),
-                           run_cap, item_cap, rpg, info, run_items, rows, items, wg_hist, (unsigned long long *)(ctx->d_totals + 6), ctx->d_flags, r_done, r_end);
+                           run_cap, item_cap, rpg, info, run_items, rows, items, wg_hist, (unsigned long long *)(ctx->d_totals + 6), ctx->d_flags, r_done, r_end, (uint32_t *)nullptr);
       r_done = r_end;
     }
   }
@@ -3105,6 +3120,36 @@ static kmi_status sk_front_fast(kmi_ctx *ctx, const kmi_config *cfg, const KShap
       hipMemcpy(t, ctx->d_flags + 48, sizeof(t), hipMemcpyDeviceToHost);
       fprintf(stderr, "sk_front wave clocks: wait-bytes %llu  eol %llu  lines %llu  load+pack %llu  walk %llu  final %llu  copy-out %llu  rest %llu\n", t[0], t[1], t[2], t[3], t[4], t[5], t[6], t[7]);
       hipMemset(ctx->d_flags + 48, 0, sizeof(t));
+    }
+#endif
+#ifdef KMI_FR_LEAVE
+    {
+      hipStreamSynchronize(ctx->stream);
+      // when the wavefronts of the (last) launch left the kernel, against the first one's entry: the spread is what a SIMD spends with
+      // fewer than its three wavefronts. By SIMD (a workgroup's wavefront w runs on SIMD w) and by workgroup order (the three
+      // workgroups of a CU are its first, second and third arrival: the oldest wavefront of a SIMD is issued first).
+      if (!fed) {
+        const uint32_t nw = std::min<uint32_t>(front_launched_waves, kFrTimingWaves);
+        std::vector<unsigned long long> wc(2 * (size_t)nw);
+        hipMemcpyFromSymbol(wc.data(), HIP_SYMBOL(g_fr_wave_clock), sizeof(unsigned long long) * wc.size());
+        unsigned long long first = ~0ull;
+        for (uint32_t i = 0; i < nw; ++i) first = std::min(first, wc[2 * i]);
+        std::vector<double> leave(nw);
+        double by_simd[kFrWaves] = {0}, by_third[3] = {0}, enter_third[3] = {0}; uint32_t n_third[3] = {0};
+        for (uint32_t i = 0; i < nw; ++i) {
+          leave[i] = (double)(wc[2 * i + 1] - first) * 0.01;   // the wall clock counts at 100 MHz: microseconds
+          by_simd[i % kFrWaves] += leave[i] / (nw / kFrWaves);
+          const uint32_t th = (uint32_t)((uint64_t)i * 3u / nw);
+          by_third[th] += leave[i]; enter_third[th] += (double)(wc[2 * i] - first) * 0.01; ++n_third[th];
+        }
+        std::vector<double> so(leave);
+        std::sort(so.begin(), so.end());
+        double mean = 0; for (double v : so) mean += v / nw;
+        fprintf(stderr, "sk_front wavefronts leave (us after the first entry): n %u  min %.1f  median %.1f  mean %.1f  max %.1f  | by SIMD %.1f %.1f %.1f %.1f"
+                        "  | by workgroup third: leave %.1f %.1f %.1f  enter %.1f %.1f %.1f\n", nw, so[0], so[nw / 2], mean, so[nw - 1], by_simd[0], by_simd[1],
+                by_simd[2], by_simd[3], by_third[0] / n_third[0], by_third[1] / n_third[1], by_third[2] / n_third[2], enter_third[0] / n_third[0],
+                enter_third[1] / n_third[1], enter_third[2] / n_third[2]);
+      }
     }
 #endif
     hipLaunchKernelGGL(sk_front_verify_kernel, dim3(1), dim3(1024), 0, ctx->stream, (const FrRange *)info, n_ranges, rpg, group_runs, ctx->d_totals + 12, ctx->d_flags);

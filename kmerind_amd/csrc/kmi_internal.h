@@ -129,6 +129,8 @@ struct kmi_ctx {
   bool front_fused = true;       // FASTQ front end of the super-k-mer build in one pass (kmi_front.h); KMI_FRONT=general: scan + list + minimizer
   uint32_t front_waves = 0;      // resident wavefronts of the front kernel (ranges of a large input); 0: not asked yet
   uint64_t front_min_range = 64ull << 10;   // smallest byte range of a wavefront (KMI_FRONT_MIN_RANGE: tests shrink it)
+  uint32_t front_ranges_per_wave = 4;       // byte ranges per resident wavefront of a large input: handed out from a queue (KMI_FRONT_RANGES_PER_WAVE)
+  uint32_t front_max_waves = 0;             // most wavefronts the front kernel is launched with; 0: as many as are resident (KMI_FRONT_MAX_WAVES: tests make few take many ranges)
   uint64_t sparse_min = 1ull << 26;   // output slots from which a super-k-mer build leaves its index in the sparse form (KMI_SPARSE_MIN)
   int sk_dbg = 0;                // KMI_SK_DBG=7 (test knob): the super-k-mer front end reports a capacity as exceeded
   bool fa_part_set = false;      // kmi_ctx_set_fasta_partition

@@ -16,6 +16,6 @@ PY
 for spec in "$@"; do
   name=${spec%%:*}; envs=${spec#*:}
   env $envs timeout -k 10 240 $B > $OUT/$name.log 2>&1 || { rc=$?; echo "$name failed rc=$rc: stopping"; tail -5 $OUT/$name.log; exit $rc; }
-  grep -h "wave clocks" $OUT/$name.log | tail -3
+  grep -h "wave clocks\|wavefronts leave" $OUT/$name.log | tail -4
   summ $OUT/$name.log
 done
