@@ -780,17 +780,33 @@ __device__ KMI_SK_PROBE_ATTR uint32_t sk_probe_insert(lds_u64_t *tkeys, lds_u32_
 
 // ---- the kernel ------------------------------------------------------------------------------------------------------
 // The two tables and the expansion described above, organised so that nothing is paid per bucket that can be paid per workgroup:
-//  * one workgroup per CU stays resident and pulls fine buckets from a queue (one atomic per bucket, issued a bucket ahead);
+//  * one workgroup per CU stays resident and pulls fine buckets from a queue: one atomic per bucket, issued TWO buckets ahead
+//    at an address the compiler cannot prove uniform (a uniform one is rewritten into the wave-aggregated form, whose
+//    v_readfirstlane makes wavefront 0 wait for the answer on the spot); the answer is first read behind phase A's record waits;
 //  * the tables are cleared ONCE; afterwards the sweep that emits a pass's (k-mer, count) pairs leaves every slot it read
 //    empty, and phase B empties every record slot it expands -- a pass starts on clean tables without a clear of its own;
 //  * records that find no room in T1 go to a short overflow list and are expanded in phase B with everything else (the
 //    direct expansions inside phase A cost a whole expansion step for the two or three records of a batch that needed one);
-//  * the first records of the NEXT bucket are loaded before the emit sweep of the current one, so a bucket does not start
-//    with two dependent trips to HBM (its offsets, then its records).
+//  * the NEXT bucket is known at the top of a bucket: its range comes by scalar loads during phase A, its first records by
+//    one load per lane behind phase B, taken in behind the barriers in front of the emit sweep (issued behind phase A
+//    instead, with all of phase B to land in, it measured the same: not kept);
+//  * every vector memory wait of the kernel is written out (vm_landed below) at a place where the loads have landed: left
+//    to the compiler, a load that MAY be in flight on some path cost a vmcnt(0) wherever one of its registers was touched next
+//    -- three times inside phase B, in front of the emit sweep (one load latency behind the prefetch's issue), and in front
+//    of a bucket's first batch of records, where wavefront 0 also waited for its ticket;
+//  * the emit sweep reads all of a thread's slots first and reserves a wavefront's output in ONE returning LDS add.
 #ifndef KMI_SK_OVF
 #define KMI_SK_OVF 448   // overflow list entries (records that T1 did not take). With H1 1536: 100 record slots + 28 list entries per wavefront in phase B = two full steps of 64 lanes; 192: 3.12 ms, 384: 2.98, 448: 2.97, 512: 3.00 (config 2)
 #endif
 constexpr int kSkOvf = KMI_SK_OVF;
+// two parts of a bucket's tail, each to be taken out again for an A/B (0): the ticket as a plain atomic, the emit sweep with
+// one allocation per wavefront
+#ifndef KMI_SK_TICKET_PLAIN
+#define KMI_SK_TICKET_PLAIN 1
+#endif
+#ifndef KMI_SK_EMIT_BLOCK
+#define KMI_SK_EMIT_BLOCK 1
+#endif
 template <int OWN_>
 struct SkTab2 {
   static constexpr int NT = KMI_SK_NT, NWAVES = NT / kWave;
@@ -854,13 +870,35 @@ __global__ __launch_bounds__(KMI_SK_NT, KMI_SK_MIN_WAVES) void sk_reduce_kernel(
   for (uint32_t i = threadIdx.x; i < (uint32_t)T::S1; i += T::NT) { s_r[i] = make_ulonglong2(kEmptyKey, W1_INIT); s_rc[i] = 0; }
   for (uint32_t i = threadIdx.x; i < (uint32_t)(NWAVES * kMissQ); i += T::NT) s_missq[i] = 0;   // (to_table2's idle compare-and-swaps land here: never the empty marker)
   if (threadIdx.x < 12) s_ctl[threadIdx.x] = 0;
-  if (threadIdx.x == 0) s_ctl[C_NEXT] = atomicAdd(queue, 1u);
+  if (threadIdx.x == 0) { s_ctl[C_NEXT] = atomicAdd(queue, 1u); s_ctl[C_NEXT + 1] = atomicAdd(queue, 1u); }
   lds_barrier();
-  uint32_t b = __builtin_amdgcn_readfirstlane(s_ctl[C_NEXT]);
-  uint32_t par = 1;                      // which of the two "next bucket" words this bucket publishes
-  bool pf_ok = false;                    // pf / pf_rb / pf_re hold the start of bucket b
+  // b is the bucket at work, b1 the one behind it; the ticket behind that is asked for at the top of b. One thread's tickets
+  // only grow: b >= n_buckets means b1 is past the end too, and a workgroup ends having seen two such tickets.
+  uint32_t b = __builtin_amdgcn_readfirstlane(s_ctl[C_NEXT]), b1 = __builtin_amdgcn_readfirstlane(s_ctl[C_NEXT + 1]);
+  uint32_t par = 0;                      // which of the two "next bucket" words this bucket publishes
+  // a wavefront's share [lo, hi) of a bucket's n records
+  auto share_of = [&](uint32_t n, uint32_t &lo, uint32_t &hi) {
+    const uint32_t share = (n + NWAVES - 1) / NWAVES;
+    lo = wv * share < n ? wv * share : n;
+    hi = lo + share < n ? lo + share : n;
+  };
+  // bucket b's range [cur_rb, cur_re), its output range [cur_k0, cur_k1) and its first records (pf: this lane's record of the
+  // wavefront's first batch; whatever a lane without one holds is never looked at)
+  uint64_t cur_rb = 0, cur_re = 0, cur_k0 = 0, cur_k1 = 0;
   ulonglong2 pf = make_ulonglong2(0, 0);
-  uint64_t pf_rb = 0, pf_re = 0, pf_k0 = 0, pf_k1 = 0;
+  if (b < n_buckets) {
+    records_of(b, cur_rb, cur_re); cur_k0 = kmer_off[b]; cur_k1 = kmer_off[b + 1];
+    uint32_t lo, hi;
+    share_of((uint32_t)(cur_re - cur_rb), lo, hi);
+    if (lo + lane < hi) pf = reinterpret_cast<const ulonglong2 *>(recs)[cur_rb + lo + lane];
+  }
+  // The vector memory counter is one number per wavefront and its answers come in order, and the compiler places its waits
+  // from what MAY be in flight on any path: a register that a load on some other path may still own costs a vmcnt(0) where it
+  // is next written or read -- and a vmcnt(0) also waits for the queue ticket and for the acknowledgements of the emit stores.
+  // So every load of this kernel is taken in by an explicit wait at a place where it has landed anyway; between those places
+  // the compiler sees nothing in flight that a register depends on and places no wait of its own.
+  auto vm_landed = [] { __builtin_amdgcn_s_waitcnt(0x0F70); };   // vmcnt(0), the other counters left alone
+  vm_landed();
   // all k-mers of a batch of records (w0, w1, weight wt; n = 0: none) into the k-mer table
   uint32_t mn = 0, pending = 0, my_claims = 0, hbits = 0, hmask = 0, hval = 0;
   // one k-mer (key, weight kw; v: it is this pass's) into the k-mer table: the home slot and the one behind it in one read, a first
@@ -1010,19 +1048,34 @@ __global__ __launch_bounds__(KMI_SK_NT, KMI_SK_MIN_WAVES) void sk_reduce_kernel(
 #define TQ_MARK(i)
 #endif
   while (b < n_buckets) {   // uniform
+    // the ticket of the bucket after next: a plain returning atomic whose answer stays in its register until phase A is done
+    // (vector memory answers come in order: phase A's record waits have taken it in by then). The empty asm hides from the
+    // compiler that the address is uniform, which keeps the atomic out of the wave-aggregated form; hiding the offset and
+    // not the pointer keeps it a global_atomic (a flat one also counts as an LDS operation, and every LDS wait would wait for it).
     uint32_t q_next = 0;
-    if (threadIdx.x == 0) q_next = atomicAdd(queue, 1u);   // (stays in a register until phase A is done: nobody waits for it)
-    uint64_t rb = pf_rb, re = pf_re;
-    if (!pf_ok) records_of(b, rb, re);
+    if (threadIdx.x == 0) {
+      uint32_t q_at = 0;
+#if KMI_SK_TICKET_PLAIN
+      asm volatile("" : "+v"(q_at));
+#endif
+      q_next = atomicAdd(queue + q_at, 1u);
+    }
+    const uint64_t rb = cur_rb, re = cur_re, tmp0 = cur_k0, tmp1 = cur_k1;
     const uint32_t n_rec = (uint32_t)(re - rb);
     const ulonglong2 *const src = reinterpret_cast<const ulonglong2 *>(recs) + rb;
-    const uint32_t share = (n_rec + NWAVES - 1) / NWAVES;
-    const uint32_t r_lo = wv * share < n_rec ? wv * share : n_rec;
-    const uint32_t r_hi = r_lo + share < n_rec ? r_lo + share : n_rec;
-    ulonglong2 first = pf;
-    if (!pf_ok) { first = make_ulonglong2(0, 0); if (r_lo + lane < r_hi) first = src[r_lo + lane]; }
-    const uint64_t tmp0 = pf_ok ? pf_k0 : kmer_off[b], tmp1 = pf_ok ? pf_k1 : kmer_off[b + 1];
-    pf_ok = false;
+    uint32_t r_lo, r_hi;
+    share_of(n_rec, r_lo, r_hi);
+    const ulonglong2 first = pf;
+    // the next bucket's range: scalar loads that return during phase A
+    uint64_t nx_rb = 0, nx_re = 0, nx_k0 = 0, nx_k1 = 0;
+    if (b1 < n_buckets) { records_of(b1, nx_rb, nx_re); nx_k0 = kmer_off[b1]; nx_k1 = kmer_off[b1 + 1]; }
+    // its first records: one unconditional load per lane, a lane without a record reads this bucket's first one (no branch
+    // around the load). Called from inside the pass loop, where this bucket has records.
+    auto prefetch_next = [&]() {
+      uint32_t nlo, nhi;
+      share_of((uint32_t)(nx_re - nx_rb), nlo, nhi);
+      pf = reinterpret_cast<const ulonglong2 *>(recs)[nlo + lane < nhi ? nx_rb + nlo + lane : rb];
+    };
     if (threadIdx.x == 0) {
       uint32_t hb = start_bits > 8u ? 8u : start_bits;
       if (use_t1_known && n_rec) {
@@ -1041,9 +1094,11 @@ __global__ __launch_bounds__(KMI_SK_NT, KMI_SK_MIN_WAVES) void sk_reduce_kernel(
 #ifdef KMI_SK_TIMING
     tq = clock64();
 #endif
-    while (true) {
+    // A bucket with records has a pass on its stack (do-while); an empty one takes the else behind the loop: every way through
+    // a bucket passes an explicit wait behind the ticket's issue. (The compiler still opens a bucket with one vmcnt(0), IN
+    // FRONT of the ticket: it waits for the acknowledgements of the previous bucket's stores, as it always did.)
+    if (n_rec != 0u) do {
       const uint32_t sp = s_ctl[C_SP];
-      if (sp == 0) break;                       // uniform
       const uint32_t pass = s_stack[sp - 1];
       const uint32_t fbits = pass & 0xffu, fval = pass >> 8;
       lds_barrier();                            // everyone has read the stack
@@ -1057,12 +1112,15 @@ __global__ __launch_bounds__(KMI_SK_NT, KMI_SK_MIN_WAVES) void sk_reduce_kernel(
       mn = 0; pending = 0; my_claims = 0;
       // ---- phase A: identical records are counted; what T1 does not take waits in the overflow list
       {
-        ulonglong2 nxt = first;
-        if (!first_pass) { nxt = make_ulonglong2(0, 0); if (r_lo + lane < r_hi) nxt = src[r_lo + lane]; }
+        // the batch at work is in `rec` with nothing in flight behind it at the head of the loop: the first batch of a bucket
+        // came with the prefetch, and wavefront 0 works on it while its ticket is still on the way (a later pass of a bucket
+        // begins with a trip to memory)
+        ulonglong2 rec = first;
+        if (!first_pass) { rec = make_ulonglong2(0, 0); if (r_lo + lane < r_hi) rec = src[r_lo + lane]; vm_landed(); }
         for (uint32_t r0 = r_lo; r0 < r_hi; r0 += kWave) {
           if (__atomic_load_n(&s_ctl[C_OVF], __ATOMIC_RELAXED)) break;   // this pass is lost already
-          const ulonglong2 rec = nxt;
           const bool have = r0 + lane < r_hi;
+          ulonglong2 nxt = rec;
           if (r0 + kWave + lane < r_hi) nxt = src[r0 + kWave + lane];   // in flight while this batch is worked on
           uint32_t n = (have && rec.y != kSkPadW1) ? ((uint32_t)(rec.y >> kRecNShift) & 31u) + 1u : 0u;
           if ((rec_hash18(rec.y) & rmask) != rval) n = 0;
@@ -1107,17 +1165,18 @@ __global__ __launch_bounds__(KMI_SK_NT, KMI_SK_MIN_WAVES) void sk_reduce_kernel(
             }
           }
           if (__any(direct)) { TQ_MARK(0) expand(rec.x, rec.y, 1u, direct ? n : 0u); TQ_MARK(1) }
+          vm_landed();   // the next batch (and, in a bucket's first pass, wavefront 0's ticket, which is older)
+          rec = nxt;
         }
       }
       TQ_MARK(0)
       if (first_pass && threadIdx.x == 0) s_ctl[C_NEXT + par] = q_next;
-      lds_barrier();   // T1 and the overflow list complete; the next bucket is known
+      lds_barrier();   // T1 and the overflow list complete; the ticket is in LDS
       TQ_MARK(2)
-      uint32_t nbk = 0;
-      if (first_pass) {   // the next bucket's range: two scalar loads that return during phase B
-        nbk = __builtin_amdgcn_readfirstlane(s_ctl[C_NEXT + par]);
-        if (nbk < n_buckets) { records_of(nbk, pf_rb, pf_re); pf_k0 = kmer_off[nbk]; pf_k1 = kmer_off[nbk + 1]; }
-      }
+      // Free here -- phase A has used everything it loaded, but for the batch a lost pass broke away from -- and it leaves
+      // nothing in flight for phase B, which issues no vector memory operation: no reuse of a phase-A register makes the
+      // compiler wait there.
+      vm_landed();
       // ---- phase B: every distinct record once with its multiplicity, then the overflow list; the slots are left empty
       if (use_t1) {
         const uint32_t n_ovf = s_ctl[C_OVN] < (uint32_t)kSkOvf ? s_ctl[C_OVN] : (uint32_t)kSkOvf;
@@ -1152,19 +1211,16 @@ __global__ __launch_bounds__(KMI_SK_NT, KMI_SK_MIN_WAVES) void sk_reduce_kernel(
         mn = 0;
       }
       if (pending && lane == 0 && atomicAdd(&s_ctl[C_DIST], pending) + pending >= (uint32_t)T::LIMIT2) s_ctl[C_OVF] = 1;
-      if (first_pass && nbk < n_buckets) {   // the next bucket's first records, in flight during the emit sweep
-        const uint32_t nn = (uint32_t)(pf_re - pf_rb), nshare = (nn + NWAVES - 1) / NWAVES;
-        const uint32_t nlo = wv * nshare < nn ? wv * nshare : nn, nhi = nlo + nshare < nn ? nlo + nshare : nn;
-        pf = make_ulonglong2(0, 0);
-        if (nlo + lane < nhi) pf = reinterpret_cast<const ulonglong2 *>(recs)[pf_rb + nlo + lane];
-        pf_ok = true;
-      }
+      if (first_pass) prefetch_next();   // lands while the wavefront waits at the two barriers below
       first_pass = false;
       TQ_MARK(3)
       lds_barrier();
       TQ_MARK(4)
       const bool lost = s_ctl[C_OVF] != 0u;
       lds_barrier();   // everyone has read the verdict (the resets below overwrite it)
+      // The prefetch is taken in here, behind the barriers and in front of the sweep's stores (and of the level votes a lost
+      // pass reads). The copy that hands it to the next bucket then needs no wait of its own.
+      vm_landed();
       if (threadIdx.x == 0) { s_ctl[C_DIST] = 0; s_ctl[C_OVF] = 0; s_ctl[C_T1N] = 0; s_ctl[C_OVN] = 0; }
       if (lost) {
         // Overflow: this pass is split -- straight to the level most buckets of this build ended at (flags[16 + L] counts the
@@ -1193,6 +1249,38 @@ __global__ __launch_bounds__(KMI_SK_NT, KMI_SK_MIN_WAVES) void sk_reduce_kernel(
       // emit behind what the earlier passes left (disjoint key sets); every slot read is left empty
       {
         uint32_t *s_out = &s_ctl[C_EMIT];
+#if KMI_SK_EMIT_BLOCK
+        // A thread reads ALL its slots first (independent reads, all in flight together); the wavefront counts the used ones
+        // of every round and reserves its whole output block in ONE returning LDS add. Round i's used lanes then write at
+        // block + (used slots of the rounds before) + (used lanes below): consecutive addresses, as before. (An allocation
+        // per round was read -> ballot -> returning add -> ds_bpermute -> store, three dependent LDS trips, seven times over.)
+        constexpr int EI = (T::S2 + T::NT - 1) / T::NT;   // S2 is a multiple of 64: a wavefront is inside the table or outside
+        uint64_t ek[EI]; uint32_t ev[EI], eo[EI];
+#pragma unroll
+        for (int i = 0; i < EI; ++i) {
+          const uint32_t s = threadIdx.x + (uint32_t)i * T::NT;
+          ek[i] = kEmptyKey; ev[i] = 0;
+          if (i < EI - 1 || s < (uint32_t)T::S2) { ek[i] = s_tk[s]; ev[i] = s_tv[s]; }
+        }
+        uint32_t total = 0;
+#pragma unroll
+        for (int i = 0; i < EI; ++i) {
+          const unsigned long long m = __ballot(ek[i] != kEmptyKey);
+          eo[i] = total + __builtin_amdgcn_mbcnt_hi((uint32_t)(m >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)m, 0u));
+          total += (uint32_t)__popcll(m);
+        }
+        uint32_t block = 0;
+        if (total) {   // uniform
+          if (lane == 0) block = atomicAdd(s_out, total);
+          block = __builtin_amdgcn_readfirstlane(block);
+        }
+        const uint64_t o0 = tmp0 + block;
+#pragma unroll
+        for (int i = 0; i < EI; ++i) {
+          const uint32_t s = threadIdx.x + (uint32_t)i * T::NT;
+          if (ek[i] != kEmptyKey) { tmp_keys[o0 + eo[i]] = ek[i]; tmp_vals[o0 + eo[i]] = ev[i]; s_tk[s] = kEmptyKey; s_tv[s] = 0; }
+        }
+#else
         for (uint32_t s = threadIdx.x; s < (uint32_t)((T::S2 + kWave - 1) / kWave * kWave); s += T::NT) {
           uint64_t key = kEmptyKey; uint32_t val = 0;
           if (s < (uint32_t)T::S2) { key = s_tk[s]; val = s_tv[s]; }
@@ -1200,6 +1288,7 @@ __global__ __launch_bounds__(KMI_SK_NT, KMI_SK_MIN_WAVES) void sk_reduce_kernel(
           const uint32_t pos = wave_alloc(s_out, used);
           if (used) { tmp_keys[tmp0 + pos] = key; tmp_vals[tmp0 + pos] = val; s_tk[s] = kEmptyKey; s_tv[s] = 0; }
         }
+#endif
         lds_barrier();
         if (threadIdx.x == 0) {
           if (s_ctl[C_SPS]) {
@@ -1213,15 +1302,22 @@ __global__ __launch_bounds__(KMI_SK_NT, KMI_SK_MIN_WAVES) void sk_reduce_kernel(
       }
       lds_barrier();
       TQ_MARK(5)
+    } while (s_ctl[C_SP] != 0u);   // uniform
+    else {   // an empty bucket has no pass: its ticket and the next bucket's first records from here
+      if (threadIdx.x == 0) s_ctl[C_NEXT + par] = q_next;
+      uint32_t nlo, nhi;
+      share_of((uint32_t)(nx_re - nx_rb), nlo, nhi);
+      if (nlo + lane < nhi) pf = reinterpret_cast<const ulonglong2 *>(recs)[nx_rb + nlo + lane];
+      vm_landed();
     }
     if (threadIdx.x == 0) {
       out_cnt[b] = s_ctl[C_EMIT];
       if (n_rec && (s_ctl[C_LVL] || start_bits)) atomicAdd(&flags[16 + (s_ctl[C_LVL] > 8u ? 8u : s_ctl[C_LVL])], 1u);
     }
-    if (n_rec == 0u && threadIdx.x == 0) s_ctl[C_NEXT + par] = q_next;   // (an empty bucket never reached the pass loop)
     lds_barrier();   // everyone has left the pass loop (the next bucket's set-up rewrites the stack words)
-    b = __builtin_amdgcn_readfirstlane(s_ctl[C_NEXT + par]);
-    par ^= 1u;
+    const uint32_t b2 = __builtin_amdgcn_readfirstlane(s_ctl[C_NEXT + par]);
+    b = b1; b1 = b2; par ^= 1u;
+    cur_rb = nx_rb; cur_re = nx_re; cur_k0 = nx_k0; cur_k1 = nx_k1;
     TQ_MARK(6)
   }
 #ifdef KMI_SK_TIMING
