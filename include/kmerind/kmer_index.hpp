@@ -719,6 +719,24 @@ class Index {
     return out;
   }
 
+  // ---- the count spectrum and the filter by count, on the device (erase_if(pred) stays the route for any other predicate).
+  // count_spectrum: out[min(count, n_bins - 1)] = number of stored keys with that count, over all ranks (collective when size() > 1).
+  std::vector<uint64_t> count_spectrum(uint32_t n_bins = 256, kmi_spectrum_totals *totals = nullptr) const {
+    static_assert(MapType::index_kind == KMI_INDEX_COUNT, "count_spectrum() is a member of the count index");
+    std::vector<uint64_t> out(n_bins);
+    if (rccl) ::kmerind::check(ctx, kmi_index_spectrum_dist_host(idx, rccl, n_bins, out.data(), totals));
+    else ::kmerind::check(ctx, kmi_index_spectrum_host(idx, n_bins, out.data(), totals));
+    return out;
+  }
+  // retain_counts: keeps the keys with lo <= count <= hi. Local on every rank (nothing is exchanged: the union of the ranks'
+  // filtered shares is the filtered map); returns this rank's erased count.
+  size_t retain_counts(uint32_t lo, uint32_t hi = UINT32_MAX) {
+    static_assert(MapType::index_kind == KMI_INDEX_COUNT, "retain_counts() is a member of the count index");
+    uint64_t n = 0;
+    ::kmerind::check(ctx, kmi_index_retain_counts(idx, lo, hi, &n));
+    return (size_t)n;
+  }
+
   kmi_ctx *context() const { return ctx; }
   const kmi_config &config() const { return cfg; }
 

@@ -100,7 +100,7 @@ kmi_status kmi_ctx_reset_hints(kmi_ctx *ctx);
  * and 3: calls that reached hipMalloc; 4: blocks taken from the process-wide cache instead; 5: pointer-jumping rounds, 6: exchanges
  * and 7: bytes this rank sent in the context's last kmi_dbg_compact_dist_host; 8: the largest number of passes a bucket needed in
  * the context's last kmi_index_lookup_* / kmi_index_profile_reads_* (1 when every bucket's entries fit one table; 0: no bucket was
- * looked at) */
+ * looked at); 9: the entry count of the fullest bucket the context's last kmi_index_retain_counts met (0: the index was empty) */
 kmi_status kmi_ctx_debug_counter(const kmi_ctx *ctx, uint32_t which, uint64_t *value);
 /* A destroyed context leaves its large device blocks (workspace, spare index arrays: >= 1 MB each, 96 GB / 64 blocks at most) in a
  * process-wide cache per device, where the next context of that device finds them: its first build then does not wait for
@@ -482,6 +482,42 @@ kmi_status kmi_index_profile_reads_dev (kmi_index *idx, const uint8_t *bytes_dev
                                         kmi_read_profile *out_dev, size_t capacity, uint64_t *n_reads);
 kmi_status kmi_index_profile_reads_host(kmi_index *idx, const uint8_t *bytes, size_t n_bytes, uint32_t solid_threshold,
                                         kmi_read_profile *out, size_t capacity, uint64_t *n_reads);
+
+/* ---- the count spectrum, and the filter by count (no counterpart in the reference beyond to_vector() plus a host loop, the way
+ * its erase_if(pred) works)
+ * Count indexes only (KMI_INDEX_COUNT); a position index gives KMI_ERR_INVALID. Every k-mer shape a count index takes (one to four
+ * words; 2-, 3- and 4-bit alphabets), both layouts, dense and sparse indexes alike (the unused slots of a sparse index are never
+ * read as entries). One rank's entries unless said otherwise.
+ *
+ * spectrum: hist[min(count, n_bins - 1)] is incremented once per stored entry: bin c < n_bins - 1 holds the entries whose count is
+ * exactly c -- bin 0 included, since update with ASSIGN or MIN can store a 0 -- and the last bin every entry with count >=
+ * n_bins - 1. All n_bins words are written (hist_dev is cleared on the context's stream inside the call); the caller need not clear
+ * them. n_bins outside 2 .. KMI_SPECTRUM_MAX_BINS gives KMI_ERR_INVALID. The index is not changed (a sparse index stays sparse); an
+ * empty index gives all zeros. _dev with totals == NULL only queues its work on the context's stream; with totals it waits.
+ *
+ * spectrum_dist_host (collective): hist, n_entries and sum_counts summed over the ranks, min_count / max_count reduced over them
+ * (ranks without entries abstain). Every key lives on exactly one rank whichever way the index was built (KeyToRank or minimizer-
+ * bucket owner), so this is the spectrum of the whole map. A rank whose local pass fails does not leave its peers waiting: they
+ * return KMI_ERR_PEER. Works over a one-rank communicator.
+ *
+ * retain_counts: keeps the entries with lo <= count <= hi and erases the rest; *n_erased = how many left. lo > hi gives
+ * KMI_ERR_INVALID and changes nothing. No key travels to the host. The survivors go, in their old order, into fresh arrays of
+ * exactly the surviving size (dropping the singletons of a read set gives most of the index's memory back); the result is a dense
+ * index in the same layout, with the same owner ranks, saturation setting and configuration, and every later operation works on it
+ * as on any index, also when nothing survived. When nothing is erased the index is left exactly as it is (a sparse one sparse).
+ * There is no _dist form because there is nothing to exchange: every rank filters its own share, and the union of the shares is
+ * the filtered map. kmi_ctx_debug_counter 9 gives the entry count of the fullest bucket the last call met. */
+enum { KMI_SPECTRUM_MAX_BINS = 65536 };
+typedef struct {
+  uint64_t n_entries;   /* entries counted = kmi_index_local_size */
+  uint64_t sum_counts;  /* sum of the stored counts, 64-bit, never clamped */
+  uint32_t min_count;   /* 0 for an empty index */
+  uint32_t max_count;   /* 0 for an empty index */
+} kmi_spectrum_totals;  /* 24 bytes */
+kmi_status kmi_index_spectrum_dev (kmi_index *idx, uint32_t n_bins, uint64_t *hist_dev, kmi_spectrum_totals *totals /* host; may be NULL */);
+kmi_status kmi_index_spectrum_host(kmi_index *idx, uint32_t n_bins, uint64_t *hist,     kmi_spectrum_totals *totals /* may be NULL */);
+kmi_status kmi_index_spectrum_dist_host(kmi_index *idx, kmi_comm *comm, uint32_t n_bins, uint64_t *hist, kmi_spectrum_totals *totals /* may be NULL */);
+kmi_status kmi_index_retain_counts(kmi_index *idx, uint32_t lo, uint32_t hi, uint64_t *n_erased /* may be NULL */);
 
 /* ---- a count index over 2, 4 or 8 ranks through exchanged super-k-mers ---------------
  * The reference's distributed insert sends every k-mer to KeyToRank(k-mer) (8 bytes per k-mer over the wire,

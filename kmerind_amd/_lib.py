@@ -47,6 +47,13 @@ class Results(C.Structure):
     _fields_ = [("n", C.c_uint64), ("keys", C.POINTER(C.c_uint64)), ("values", C.POINTER(C.c_uint64))]
 
 
+class SpectrumTotals(C.Structure):
+    _fields_ = [("n_entries", C.c_uint64), ("sum_counts", C.c_uint64), ("min_count", C.c_uint32), ("max_count", C.c_uint32)]
+
+
+SPECTRUM_MAX_BINS = 65536
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char_p), ("total_ms", C.c_double), ("launches", C.c_uint64), ("units", C.c_uint64)]
 
@@ -148,6 +155,10 @@ SIGNATURES = {
     "kmi_index_lookup_host": (C.c_int, [_P, _P, _sz, _P]),
     "kmi_index_profile_reads_dev": (C.c_int, [_P, _P, _sz, _u32, _P, _sz, C.POINTER(_u64)]),
     "kmi_index_profile_reads_host": (C.c_int, [_P, _P, _sz, _u32, _P, _sz, C.POINTER(_u64)]),
+    "kmi_index_spectrum_dev": (C.c_int, [_P, _u32, _P, C.POINTER(SpectrumTotals)]),
+    "kmi_index_spectrum_host": (C.c_int, [_P, _u32, _P, C.POINTER(SpectrumTotals)]),
+    "kmi_index_spectrum_dist_host": (C.c_int, [_P, _P, _u32, _P, C.POINTER(SpectrumTotals)]),
+    "kmi_index_retain_counts": (C.c_int, [_P, _u32, _u32, C.POINTER(_u64)]),
     "kmi_index_sk_produce_dev": (C.c_int, [_P, _P, _sz, _u32, _P, _sz, C.POINTER(_P), C.POINTER(_u64), _P, C.POINTER(C.c_int)]),
     "kmi_index_sk_consume_dev": (C.c_int, [_P, _P, _sz, _u32]),
     "kmi_route_owner_dev": (C.c_int, [_P, _CFG, _P, _sz, _u32, _P, _P]),

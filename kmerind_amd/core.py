@@ -365,6 +365,31 @@ class CountIndex:
             raise err
         return n.value
 
+    # ---- the count spectrum and the filter by count (kmi_index_spectrum_* / kmi_index_retain_counts)
+    @staticmethod
+    def _totals(t):
+        return {"n_entries": t.n_entries, "sum_counts": t.sum_counts, "min_count": t.min_count, "max_count": t.max_count}
+
+    def spectrum(self, n_bins=256):
+        """(hist, totals): hist[min(count, n_bins - 1)] counts the stored entries (np.uint64[n_bins]); totals is a dict of
+        n_entries, sum_counts, min_count, max_count"""
+        hist = np.ones(max(int(n_bins), 0), dtype=np.uint64)
+        t = L.SpectrumTotals()
+        self.ctx.check(lib.kmi_index_spectrum_host(self.h, n_bins, hist.ctypes.data_as(C.c_void_p), C.byref(t)))
+        return hist, self._totals(t)
+
+    def spectrum_device(self, hist_dptr, n_bins):
+        """hist_dptr: room for n_bins u64 on the device (cleared by the call) -> totals"""
+        t = L.SpectrumTotals()
+        self.ctx.check(lib.kmi_index_spectrum_dev(self.h, n_bins, C.c_void_p(hist_dptr), C.byref(t)))
+        return self._totals(t)
+
+    def retain_counts(self, lo, hi=2**32 - 1):
+        """keeps the entries with lo <= count <= hi, on the device -> number of entries erased"""
+        n = C.c_uint64()
+        self.ctx.check(lib.kmi_index_retain_counts(self.h, lo, hi, C.byref(n)))
+        return n.value
+
 
 class PositionIndex(CountIndex):
     """bliss::index::kmer::PositionIndex<unordered_multimap> on one rank (kmer_index.hpp:402-403):

@@ -25,7 +25,7 @@ namespace {
 typedef int ncclResult_t_;            // ncclSuccess == 0
 typedef struct { char internal[128]; } ncclUniqueId_;
 typedef void *ncclComm_t_;
-enum { kNcclUint8 = 1, kNcclUint64 = 5, kNcclSum = 0 };   // rccl.h: ncclDataType_t / ncclRedOp_t
+enum { kNcclUint8 = 1, kNcclUint64 = 5, kNcclSum = 0, kNcclMax = 2 };   // rccl.h: ncclDataType_t / ncclRedOp_t
 
 struct RcclApi {
   void *lib = nullptr;
@@ -322,17 +322,27 @@ kmi_status comm_exchange_wait(kmi_comm *c) {
   return KMI_OK;
 }
 
-kmi_status comm_allreduce_sum(kmi_comm *c, uint64_t *value) {
+kmi_status comm_allreduce(kmi_comm *c, uint64_t *values, size_t n, int op) {
   kmi_ctx *ctx = c->ctx;
-  if (c->nranks == 1) return KMI_OK;
+  if (c->nranks == 1 || n == 0) return KMI_OK;
   const int p = c->nranks;
-  if (c->has_transport) return c->transport.allreduce_u64(c->transport.user, value, 1, 0) != 0 ? tp_fail(c, "allreduce_u64") : KMI_OK;
-  c->h_small[4 * p] = *value;
-  KMI_HIP(ctx, hipMemcpyAsync(c->d_small + 4 * p, c->h_small + 4 * p, sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-  KMI_NCCL(c, rccl().AllReduce(c->d_small + 4 * p, c->d_small + 4 * p + 1, 1, kNcclUint64, kNcclSum, c->nccl, ctx->stream));
-  KMI_HIP(ctx, hipMemcpyAsync(c->h_small + 4 * p + 1, c->d_small + 4 * p + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (c->has_transport) return c->transport.allreduce_u64(c->transport.user, values, n, op) != 0 ? tp_fail(c, "allreduce_u64") : KMI_OK;
+  // up to four words go through the communicator's own scratch and its pinned mirror (send at 4p, receive behind it), more
+  // through the workspace and the caller's memory
+  uint64_t *d_s = c->d_small + 4 * p, *d_r = d_s + n, *h_s = values, *h_r = values;
+  if (n <= 4) {
+    h_s = c->h_small + 4 * p; h_r = h_s + n;
+    memcpy(h_s, values, n * sizeof(uint64_t));
+  } else {
+    void *w;
+    KMI_TRY(ws_get(ctx, WS_DIST_A, 2 * n * sizeof(uint64_t), &w));
+    d_s = (uint64_t *)w; d_r = d_s + n;
+  }
+  KMI_HIP(ctx, hipMemcpyAsync(d_s, h_s, n * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+  KMI_NCCL(c, rccl().AllReduce(d_s, d_r, n, kNcclUint64, op ? kNcclMax : kNcclSum, c->nccl, ctx->stream));
+  KMI_HIP(ctx, hipMemcpyAsync(h_r, d_r, n * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
   KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  *value = c->h_small[4 * p + 1];
+  if (n <= 4) memcpy(values, h_r, n * sizeof(uint64_t));
   return KMI_OK;
 }
 

@@ -4329,6 +4329,7 @@ static bool sk_rank_count(uint32_t p) { return p == 1u || p == 2u || p == 4u || 
 #include "kmi_unitig_dist.h"
 #include "kmi_update.h"
 #include "kmi_lookup.h"
+#include "kmi_spectrum.h"
 
 struct kmi_comm;
 static kmi_status dist_state(kmi_index *idx, kmi_comm *comm, uint64_t *holders, uint64_t *owner_p, uint64_t *owner_any);
@@ -5976,6 +5977,70 @@ kmi_status kmi_index_profile_reads_dev(kmi_index *idx, const uint8_t *bytes_dev,
 kmi_status kmi_index_profile_reads_host(kmi_index *idx, const uint8_t *bytes, size_t n_bytes, uint32_t solid_threshold, kmi_read_profile *out,
                                         size_t capacity, uint64_t *n_reads) {
   return profile_reads_entry(idx, bytes, n_bytes, false, solid_threshold, out, capacity, n_reads);
+}
+
+// ---- count spectrum and count filter (kmi_spectrum.h)
+static kmi_status spectrum_entry(kmi_index *idx, uint32_t n_bins, uint64_t *hist, bool on_device, kmi_spectrum_totals *totals) {
+  if (!idx) return KMI_ERR_INVALID;
+  kmi_ctx *ctx = idx->ctx;
+  if (idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "spectrum() is a member of the count index");
+  if (n_bins < 2 || n_bins > (uint32_t)KMI_SPECTRUM_MAX_BINS) return set_err(ctx, KMI_ERR_INVALID, "n_bins is 2 .. KMI_SPECTRUM_MAX_BINS");
+  if (!hist) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
+  KMI_HIP(ctx, hipSetDevice(ctx->device));
+  uint64_t *d_hist = hist;
+  if (!on_device) {
+    void *p;
+    KMI_TRY(ws_get(ctx, WS_OUTPUT, n_bins * sizeof(uint64_t), &p));
+    d_hist = (uint64_t *)p;
+  }
+  KMI_TRY(spectrum_run(idx, n_bins, d_hist));
+  if (!on_device) KMI_HIP(ctx, hipMemcpyAsync(hist, d_hist, n_bins * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (totals) KMI_TRY(spectrum_totals(idx, totals));
+  else if (!on_device) KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return KMI_OK;
+}
+kmi_status kmi_index_spectrum_dev(kmi_index *idx, uint32_t n_bins, uint64_t *hist_dev, kmi_spectrum_totals *totals) {
+  return spectrum_entry(idx, n_bins, hist_dev, true, totals);
+}
+kmi_status kmi_index_spectrum_host(kmi_index *idx, uint32_t n_bins, uint64_t *hist, kmi_spectrum_totals *totals) {
+  return spectrum_entry(idx, n_bins, hist, false, totals);
+}
+
+kmi_status kmi_index_spectrum_dist_host(kmi_index *idx, kmi_comm *comm, uint32_t n_bins, uint64_t *hist, kmi_spectrum_totals *totals) {
+  KMI_TRY(dist_check(idx, comm));
+  kmi_ctx *ctx = idx->ctx;
+  // (argument errors are every rank's alike: nothing collective has started)
+  if (idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "spectrum() is a member of the count index");
+  if (n_bins < 2 || n_bins > (uint32_t)KMI_SPECTRUM_MAX_BINS) return set_err(ctx, KMI_ERR_INVALID, "n_bins is 2 .. KMI_SPECTRUM_MAX_BINS");
+  if (!hist) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
+  // the bins, then n_entries and sum_counts: one sum over the ranks; the largest count and ~(the smallest): one maximum
+  std::vector<uint64_t> words((size_t)n_bins + 2, 0);
+  kmi_spectrum_totals t{};
+  const kmi_status mine = spectrum_entry(idx, n_bins, words.data(), false, &t);
+  KMI_TRY(dist_agree(comm, mine));   // a rank whose pass failed does not leave the others in the all-reduce
+  words[n_bins] = t.n_entries; words[(size_t)n_bins + 1] = t.sum_counts;
+  uint64_t ext[2] = {t.max_count, t.n_entries ? (uint64_t)(uint32_t)~t.min_count : 0ull};   // (a rank without entries has no say in either)
+  KMI_TRY(kmi::comm_allreduce_sum(comm, words.data(), words.size()));
+  KMI_TRY(kmi::comm_allreduce(comm, ext, 2, 1));
+  memcpy(hist, words.data(), sizeof(uint64_t) * n_bins);
+  if (totals) {
+    totals->n_entries = words[n_bins]; totals->sum_counts = words[(size_t)n_bins + 1];
+    totals->max_count = (uint32_t)ext[0];
+    totals->min_count = totals->n_entries ? ~(uint32_t)ext[1] : 0u;
+  }
+  return KMI_OK;
+}
+
+kmi_status kmi_index_retain_counts(kmi_index *idx, uint32_t lo, uint32_t hi, uint64_t *n_erased) {
+  if (!idx) return KMI_ERR_INVALID;
+  kmi_ctx *ctx = idx->ctx;
+  if (n_erased) *n_erased = 0;
+  if (idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "retain_counts() is a member of the count index");
+  if (lo > hi) return set_err(ctx, KMI_ERR_INVALID, "retain_counts: lo > hi");
+  ctx->retain_fullest = 0;
+  if (!idx->has_data || idx->n_entries == 0) return KMI_OK;
+  KMI_HIP(ctx, hipSetDevice(ctx->device));
+  return index_retain_counts(idx, lo, hi, n_erased);
 }
 
 }  // extern "C"

@@ -65,6 +65,7 @@ enum WsSlot {
   WS_UNI_CNT,         // ... records per destination rank, cursors, device scalars
   WS_LOOKUP_RECS,     // positional lookup / read profile (kmi_lookup.h): (key words, tag) records of the queries or of a batch's k-mers
   WS_LOOKUP_CNT,      // ... the looked-up count of every k-mer of a batch, in file order
+  WS_SPECTRUM,        // count spectrum / count filter (kmi_spectrum.h): the call's device scalars, then the survivors of every fine bucket
   WS_NUM_SLOTS
 };
 
@@ -138,6 +139,7 @@ struct kmi_ctx {
   uint32_t lookup_cap = 0;       // home slots of bucket_lookup_kernel's table (KMI_LOOKUP_CAP: tests reach the multi-pass code with a small index); 0: the table's own
   size_t profile_batch = (size_t)256 << 20;   // input bytes of a batch of kmi_index_profile_reads_* (KMI_PROFILE_BATCH)
   uint64_t lookup_npass = 0;     // the largest pass count a bucket used in the last lookup / profile (kmi_ctx_debug_counter 8)
+  uint64_t retain_fullest = 0;   // entries of the fullest bucket the last kmi_index_retain_counts met (kmi_ctx_debug_counter 9)
   int fa_left_carry = -1;        // de Bruijn tuples of a FASTA block (kmi_dbg_build_fasta_range_dist_host): the raw byte of the sequence
                                  // character before the block's first one, the in-edge of its first window; -1: none
 };
@@ -291,7 +293,10 @@ inline kmi_status align_input(kmi_ctx *ctx, const uint8_t **bytes_dev, size_t n_
 kmi_status comm_all_to_all_counts(kmi_comm *c, const uint64_t *send_counts, uint64_t *recv_counts);
 kmi_status comm_all_to_all_v(kmi_comm *c, const void *send_dev, const uint64_t *send_counts, void *recv_dev, const uint64_t *recv_counts,
                              size_t elem_bytes);
-kmi_status comm_allreduce_sum(kmi_comm *c, uint64_t *value);
+// values[0, n) (host) := their sum (op 0) or maximum (op 1) over the ranks: one callback call of a transport, one ncclAllReduce else
+// (more than four words are staged in WS_DIST_A: a caller with that many keeps nothing of its own there)
+kmi_status comm_allreduce(kmi_comm *c, uint64_t *values, size_t n, int op);
+inline kmi_status comm_allreduce_sum(kmi_comm *c, uint64_t *values, size_t n = 1) { return comm_allreduce(c, values, n, 0); }
 kmi_status comm_allgather_words(kmi_comm *c, const uint64_t *mine, size_t n, uint64_t *all);
 kmi_status comm_all_to_all_counts2(kmi_comm *c, const uint64_t *send_counts, uint64_t my_largest_bytes, uint64_t *recv_counts, uint64_t *largest_bytes);
 kmi_status comm_all_to_all_v_async(kmi_comm *c, const void *send_dev, const uint64_t *send_counts, void *recv_dev, const uint64_t *recv_counts,

@@ -26,6 +26,7 @@ run "de Bruijn nodes" python tools/dbg_bench.py
 run "de Bruijn nodes of config 2's input" python tools/dbg_bench.py 10000000 100000000
 echo "## de Bruijn nodes of config 2's input, tuple path (KMI_DBG_SUPERKMER=0)" >> $T
 KMI_DBG_SUPERKMER=0 timeout -k 10 400 python tools/dbg_bench.py 10000000 100000000 2>&1 | grep -v "amdgpu.ids" | head -2 >> $T
+run "count spectrum and count filter of config 2's index against the host routes" python tools/spectrum_bench.py
 run "config 2 from pinned host memory (kmi_index_build_host)" python tools/host_build_probe.py
 run "two builds of config 2 on two streams" python tools/overlap_probe.py
 echo "## write runs of a partition pass: aligned lines against runs that start anywhere (tools/write_runs.hip)" >> $T
