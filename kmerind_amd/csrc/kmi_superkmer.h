@@ -787,6 +787,8 @@ __device__ KMI_SK_PROBE_ATTR uint32_t sk_probe_insert(lds_u64_t *tkeys, lds_u32_
 //    empty, and phase B empties every record slot it expands -- a pass starts on clean tables without a clear of its own;
 //  * records that find no room in T1 go to a short overflow list and are expanded in phase B with everything else (the
 //    direct expansions inside phase A cost a whole expansion step for the two or three records of a batch that needed one);
+//  * phase A counts a batch's records in T1 without a branch per case: selects, one compare-and-swap and one add for all 64
+//    lanes, the rare cases behind one vote; the fill level is read as late as it can be (see the loop);
 //  * the NEXT bucket is known at the top of a bucket: its range comes by scalar loads during phase A, its first records by
 //    one load per lane behind phase B, taken in behind the barriers in front of the emit sweep (issued behind phase A
 //    instead, with all of phase B to land in, it measured the same: not kept);
@@ -899,6 +901,7 @@ __global__ __launch_bounds__(KMI_SK_NT, KMI_SK_MIN_WAVES) void sk_reduce_kernel(
   // the compiler sees nothing in flight that a register depends on and places no wait of its own.
   auto vm_landed = [] { __builtin_amdgcn_s_waitcnt(0x0F70); };   // vmcnt(0), the other counters left alone
   vm_landed();
+  auto lds_landed = [] { __builtin_amdgcn_s_waitcnt(0xC07F); };   // lgkmcnt(0), the other counters left alone
   // all k-mers of a batch of records (w0, w1, weight wt; n = 0: none) into the k-mer table
   uint32_t mn = 0, pending = 0, my_claims = 0, hbits = 0, hmask = 0, hval = 0;
   // one k-mer (key, weight kw; v: it is this pass's) into the k-mer table: the home slot and the one behind it in one read, a first
@@ -1126,42 +1129,88 @@ __global__ __launch_bounds__(KMI_SK_NT, KMI_SK_MIN_WAVES) void sk_reduce_kernel(
           if ((rec_hash18(rec.y) & rmask) != rval) n = 0;
           bool direct = n != 0u;   // still to be placed
           if (use_t1) {
-            if (direct && rec.x != kEmptyKey) {
-              // four consecutive slots in one go (independent reads): the first that holds this record takes the count, else the
-              // first empty one is claimed; a second window of four for the few that find the first one taken
-              uint32_t h = ((uint32_t)rec.x ^ (uint32_t)(rec.x >> 32)) * 0x9E3779B1u ^ ((uint32_t)rec.y ^ (uint32_t)(rec.y >> 32)) * 0x85EBCA6Bu;
-              h ^= h >> 15;
-              const uint32_t s0 = ((h >> 16) * (uint32_t)T::H1) >> 16;   // H1 home slots (+ 64 of padding)
-              for (uint32_t s = s0; direct && s < s0 + 8u; s += 4u) {
-                ulonglong2 e[4];
+            // The common case -- a record that finds itself, or an empty slot, in its first window of four slots -- is straight-line
+            // code for all 64 lanes: selects instead of a branch per case (hit / free slot / limit / claimed / lost to a copy), ONE
+            // compare-and-swap, ONE add; everything else leaves through one wavefront vote. (A branch per case: 177 instructions
+            // per batch of which 11 saved and 15 branched on the exec mask; 156, 4 and 8 so.) What this relies on, as the branching
+            // form did: a slot whose .x is claimed and whose .y is not yet stored matches nobody (.y is W1_INIT, never a record's
+            // second word), so a record may sit in T1 twice, or go to the list although a copy is in T1 -- it is never lost and
+            // never counted twice, and phase B gives every copy's k-mers their counts: the index does not depend on which happens.
+            uint32_t h = ((uint32_t)rec.x ^ (uint32_t)(rec.x >> 32)) * 0x9E3779B1u ^ ((uint32_t)rec.y ^ (uint32_t)(rec.y >> 32)) * 0x85EBCA6Bu;
+            h ^= h >> 15;
+            const uint32_t s0 = ((h >> 16) * (uint32_t)T::H1) >> 16;   // H1 home slots (+ 64 of padding); a lane without a record reads some window too
+            ulonglong2 e[4];
+#pragma unroll
+            for (int i = 0; i < 4; ++i) e[i] = s_r[s0 + i];
+            // The fill level is read BEHIND the window, as late as it can be, and fresh with every batch: the other 15 wavefronts
+            // claim slots all the while, and every claim past L1 makes the windows fuller for everyone. (Read together with the
+            // window, one round trip less: 0.05 ms slower on config 2; in one 64-bit word with the lost-pass flag, the flag acted
+            // on a batch late: 0.10 ms slower, and 1 % slower where T1 is not used.)
+            lds_landed();
+            const uint32_t t1n = __atomic_load_n(&s_ctl[C_T1N], __ATOMIC_RELAXED);
+            const bool cand = direct && rec.x != kEmptyKey;   // (a record whose first word is the empty marker goes to the list)
+            uint32_t at = 4u; bool same_at = false;          // the earliest slot that holds this record or is empty, and which of the two
+#pragma unroll
+            for (int i = 3; i >= 0; --i) {
+              const bool same = e[i].x == rec.x && e[i].y == rec.y, empty = e[i].x == kEmptyKey;
+              at = (same || empty) ? (uint32_t)i : at;
+              same_at = same ? true : (empty ? false : same_at);
+            }
+            const bool full = cand && at == 4u;                 // a window of other records: the second window, below
+            const bool hit = cand && same_at;
+            const bool may_claim = cand && !same_at && at < 4u && t1n < (uint32_t)T::L1;
+            const uint32_t slot = s0 + (at & 3u);
+            // a lane with nothing to claim aims its compare-and-swap at its word of the miss queue (never the empty marker, as in
+            // to_table2)
+            const unsigned long long old = atomicCAS(may_claim ? &s_r[slot].x : (unsigned long long *)cas_dummy, (unsigned long long)kEmptyKey, (unsigned long long)rec.x);
+            const bool won = may_claim && old == kEmptyKey;
+            if (won) __atomic_store_n(&s_r[slot].y, rec.y, __ATOMIC_RELAXED);
+            // lost the slot to a copy of the same record that arrived in the same step: counted with it if its second word is there
+            // (a winner of this wavefront has stored it above; another wavefront's may not have yet). Only batches with such a lane
+            // pay this trip.
+            bool twin = may_claim && old == rec.x;
+            if (__any(twin)) twin = twin && __atomic_load_n(&s_r[slot].y, __ATOMIC_RELAXED) == rec.y;
+            const bool counted = hit || won || twin;
+            atomicAdd(&s_rc[slot], counted ? 1u : 0u);   // (unconditional: adding zero harms no slot)
+            const unsigned long long wm = __ballot(won);
+            if (wm && lane == 0) atomicAdd(&s_ctl[C_T1N], (uint32_t)__popcll(wm));
+            direct = direct && !counted;
+            // ---- the vote: a full first window, a slot lost to another record, T1 at its limit, a first word that is the
+            // empty marker
+            if (__any(direct)) {
+              if (full) {
+                const uint32_t s = s0 + 4u;
 #pragma unroll
                 for (int i = 0; i < 4; ++i) e[i] = s_r[s + i];
-                int hit = -1, free_ = -1;
+                int hit2 = -1, free_ = -1;
 #pragma unroll
                 for (int i = 3; i >= 0; --i) {
                   const bool same = e[i].x == rec.x && e[i].y == rec.y, empty = e[i].x == kEmptyKey;
-                  if (same) { hit = i; free_ = -1; } else if (empty) { free_ = i; hit = -1; }   // (the earliest of either kind wins)
+                  if (same) { hit2 = i; free_ = -1; } else if (empty) { free_ = i; hit2 = -1; }   // (the earliest of either kind wins)
                 }
-                if (hit >= 0) { atomicAdd(&s_rc[s + hit], 1u); direct = false; }
-                else if (free_ >= 0) {
-                  if (__atomic_load_n(&s_ctl[C_T1N], __ATOMIC_RELAXED) >= (uint32_t)T::L1) break;   // full enough
-                  const unsigned long long old = atomicCAS((unsigned long long *)&s_r[s + free_].x, (unsigned long long)kEmptyKey, (unsigned long long)rec.x);
-                  if (old == kEmptyKey) {   // claimed
+                if (hit2 >= 0) { atomicAdd(&s_rc[s + hit2], 1u); direct = false; }
+                else if (free_ >= 0 && __atomic_load_n(&s_ctl[C_T1N], __ATOMIC_RELAXED) < (uint32_t)T::L1) {
+                  const unsigned long long old2 = atomicCAS((unsigned long long *)&s_r[s + free_].x, (unsigned long long)kEmptyKey, (unsigned long long)rec.x);
+                  if (old2 == kEmptyKey) {   // claimed
                     __atomic_store_n(&s_r[s + free_].y, rec.y, __ATOMIC_RELAXED);
                     atomicAdd(&s_rc[s + free_], 1u);
                     atomicAdd(&s_ctl[C_T1N], 1u);
                     direct = false;
-                  } else if (old == rec.x && __atomic_load_n(&s_r[s + free_].y, __ATOMIC_RELAXED) == rec.y) {
-                    // lost the slot to a copy of the same record that arrived in the same step: counted with it
+                  } else if (old2 == rec.x && __atomic_load_n(&s_r[s + free_].y, __ATOMIC_RELAXED) == rec.y) {
                     atomicAdd(&s_rc[s + free_], 1u);
                     direct = false;
-                  } else break;   // lost it to another record
+                  }
                 }
               }
-            }
-            if (direct) {   // the overflow list takes it (phase B expands it with weight 1)
-              const uint32_t oi = atomicAdd(&s_ctl[C_OVN], 1u);
-              if (oi < (uint32_t)kSkOvf) { s_ovf[oi] = rec; direct = false; }
+              // the overflow list takes what is left (phase B expands it with weight 1), a wavefront's entries reserved in one
+              // returning add; what the list has no room for is expanded below
+              const unsigned long long dm = __ballot(direct);
+              if (dm) {   // uniform
+                uint32_t base = 0;
+                if (lane == 0) base = atomicAdd(&s_ctl[C_OVN], (uint32_t)__popcll(dm));
+                const uint32_t oi = __builtin_amdgcn_readfirstlane(base) + __builtin_amdgcn_mbcnt_hi((uint32_t)(dm >> 32), __builtin_amdgcn_mbcnt_lo((uint32_t)dm, 0u));
+                if (direct && oi < (uint32_t)kSkOvf) { s_ovf[oi] = rec; direct = false; }
+              }
             }
           }
           if (__any(direct)) { TQ_MARK(0) expand(rec.x, rec.y, 1u, direct ? n : 0u); TQ_MARK(1) }
