@@ -252,19 +252,19 @@ kmi_status kmi_ctx_create(int device, int rank, int nranks, void *stream, kmi_ct
   if (const char *lc = getenv("KMI_LOOKUP_CAP")) { ctx->lookup_cap = (uint32_t)strtoul(lc, nullptr, 10); if (ctx->lookup_cap < 64) ctx->lookup_cap = 64; }   // (the upper bound is the table's: kmi_lookup.h)
   if (const char *pb = getenv("KMI_PROFILE_BATCH")) { ctx->profile_batch = strtoull(pb, nullptr, 10); if (ctx->profile_batch < 4096) ctx->profile_batch = 4096; }
   ctx->device = device; ctx->rank = rank; ctx->nranks = nranks; ctx->stream = (hipStream_t)stream;
-  if (hipMalloc((void **)&ctx->d_flags, sizeof(uint32_t) * 64) != hipSuccess ||
-      hipMalloc((void **)&ctx->d_totals, sizeof(uint64_t) * (16 + 256)) != hipSuccess ||
-      hipHostMalloc((void **)&ctx->h_totals, sizeof(uint64_t) * (16 + 1024), hipHostMallocDefault)   /* 16 words of totals + a mailbox for the front end's read-back */ != hipSuccess) {
+  if (hipMalloc((void **)&ctx->d_flags, sizeof(uint32_t) * kmi::FLAG_NUM_WORDS) != hipSuccess ||
+      hipMalloc((void **)&ctx->d_totals, sizeof(uint64_t) * kmi::TOT_NUM_WORDS) != hipSuccess ||
+      hipHostMalloc((void **)&ctx->h_totals, sizeof(uint64_t) * kmi::H_NUM_WORDS, hipHostMallocDefault)   /* 16 words of totals + a mailbox for the front end's read-back */ != hipSuccess) {
     delete ctx;
     return KMI_ERR_DEVICE;
   }
-  (void)hipMemset(ctx->d_flags, 0, sizeof(uint32_t) * 64);
+  (void)hipMemset(ctx->d_flags, 0, sizeof(uint32_t) * kmi::FLAG_NUM_WORDS);
   {
     hipDeviceProp_t prop;
     if (hipGetDeviceProperties(&prop, device) == hipSuccess && prop.multiProcessorCount > 0) ctx->n_cus = (uint32_t)prop.multiProcessorCount;
   }
   if (upload_quality_lut(ctx) != KMI_OK) { kmi_ctx_destroy(ctx); return KMI_ERR_DEVICE; }
-  (void)hipMemset(ctx->d_totals, 0, sizeof(uint64_t) * (16 + 256));
+  (void)hipMemset(ctx->d_totals, 0, sizeof(uint64_t) * kmi::TOT_NUM_WORDS);
   *out = ctx;
   return KMI_OK;
 }

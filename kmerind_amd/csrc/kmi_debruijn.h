@@ -523,19 +523,24 @@ static kmi_status dbg_insert(kmi_dbg *g, const uint64_t *recs_dev, size_t n) { K
 // end as it is -- the node index with its occurrence counts --, then sk_edges_accumulate over the fine buckets' records, which are
 // still in the workspace. *done = false: not this path's input (several runs per read, a base that is not A C G T, a shape without
 // super-k-mers, anything the fast front end declines): the tuple path takes it.
-template <int W>
-static kmi_status dbg_build_superkmer_w(kmi_dbg *g, const uint8_t *bytes_dev, size_t n_bytes, bool *done) {
+static kmi_status dbg_build_superkmer(kmi_dbg *g, const uint8_t *bytes_dev, size_t n_bytes, bool *done) {
+  *done = false;
   kmi_ctx *ctx = g->ctx;
   kmi_index *idx = g->nodes;
+  // (the graph's own format word, an empty graph, and an input the one-pass front end looks at)
+  if (!ctx->dbg_superkmer || g->cfg.seq_format != KMI_FMT_FASTQ || (idx->has_data && idx->n_entries) || n_bytes < 64) return KMI_OK;
+  const uint32_t w = sk_width(idx, SK_FASTQ_ONE_PASS);
+  if (!w) return KMI_OK;
+  KMI_TRY(align_input(ctx, &bytes_dev, n_bytes));
   SkFront f;
-  bool took = false;
-  ctx->edge_records = true;
-  kmi_status st = sk_front_fast<W>(ctx, &idx->cfg, idx->shape, bytes_dev, n_bytes, 0u, &f, &took);
+  SkDoor door;
+  ctx->edge_records = true;   // (the door then never opens the general front end, which makes no edge records)
+  const kmi_status st = sk_dispatch_w(w, [&](auto W) { return sk_front_door<W>(ctx, &idx->cfg, idx->shape, bytes_dev, n_bytes, 0u, &f, &door); });
   ctx->edge_records = false;
-  if (st != KMI_OK || !took || !f.ok) return st;
+  if (st != KMI_OK || door == SK_NOT_THIS_PATH) return st;
   *done = true;
-  if (f.n_kmers == 0) return KMI_OK;
-  KMI_TRY((sk_back_end<W>(idx, f.recs, f.n_records, f.h_cnt, f.h_base, f.wg_off, f.n_kmers, 0u)));
+  if (door == SK_NO_KMERS) return KMI_OK;
+  KMI_TRY(sk_back(idx, w, f, 0u));
   if (!ctx->sk_left.valid) return set_err(ctx, KMI_ERR_DEVICE, "the back end left no record of its fine buckets");
   KMI_TRY(ensure_dense(idx));
   const size_t eb = (size_t)(idx->n_entries ? idx->n_entries : 1) * 8 * sizeof(uint32_t);
@@ -553,19 +558,6 @@ static kmi_status dbg_build_superkmer_w(kmi_dbg *g, const uint8_t *bytes_dev, si
   if (g->edges) pool_free(ctx, g->edges, g->edges_bytes);
   g->edges = ne; g->edges_bytes = eb;
   return KMI_OK;
-}
-static kmi_status dbg_build_superkmer(kmi_dbg *g, const uint8_t *bytes_dev, size_t n_bytes, bool *done) {
-  *done = false;
-  kmi_ctx *ctx = g->ctx;
-  kmi_index *idx = g->nodes;
-  if (!ctx->dbg_superkmer || !ctx->fused_superkmer || !ctx->front_fused || g->cfg.seq_format != KMI_FMT_FASTQ || (idx->has_data && idx->n_entries) ||
-      idx->shape.n_words != 1 || idx->shape.bits != 2 || n_bytes < 64)
-    return KMI_OK;
-  const uint32_t w = sk_window_of(idx->shape.k);
-  if (!w) return KMI_OK;
-  KMI_TRY(align_input(ctx, &bytes_dev, n_bytes));
-  return w == 19u ? dbg_build_superkmer_w<19>(g, bytes_dev, n_bytes, done) : (w == 13u ? dbg_build_superkmer_w<13>(g, bytes_dev, n_bytes, done)
-       : (w == 11u ? dbg_build_superkmer_w<11>(g, bytes_dev, n_bytes, done) : dbg_build_superkmer_w<7>(g, bytes_dev, n_bytes, done)));
 }
 
 // nodes.erase(keys) (the erase of the distributed map the node map derives from, distributed_unordered_map.hpp:719-779): the nodes of

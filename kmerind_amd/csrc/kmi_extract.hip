@@ -77,7 +77,7 @@ __global__ __launch_bounds__((Cfg::NT)) void fastq_scan_tiles_kernel(const uint8
     }
   }
   // get_next_record refuses a partition that does not begin with '@' (fastq_loader.hpp:392-393)
-  if (blockIdx.x == 0 && threadIdx.x == 0 && (dw[0] & 0xffu) != '@') atomicOr(&flags[0], 1u);
+  if (blockIdx.x == 0 && threadIdx.x == 0 && (dw[0] & 0xffu) != '@') atomicOr(&flags[FLAG_PARSE], 1u);
   lo = wave_reduce_sum(lo); hi = wave_reduce_sum(hi);
   if (lane_id() == 0) { atomicAdd(&s_cnt[0], lo); atomicAdd(&s_cnt[1], hi); }
   lds_barrier();
@@ -99,7 +99,7 @@ __global__ __launch_bounds__((Cfg::NT)) void fastq_scan_tiles_kernel(const uint8
 //   (a) every block of 1024 tiles reduces to one summary,
 //   (b) one workgroup scans the block summaries,
 //   (c) every block re-scans its tiles from the block's base.
-// totals[0] = lines, totals[1] = tuples, totals[2] = sequences (lines with index % 4 == 1)
+// totals[TOT_LINES] = lines, totals[TOT_TUPLES] = tuples, totals[TOT_SEQS] = sequences (lines with index % 4 == 1)
 // ---------------------------------------------------------------------------
 struct TileSum { uint64_t lines; uint64_t cnt[4]; uint64_t hdr[4]; };   // hdr: 1 + byte position of the last header line start, by incoming phase
 
@@ -157,9 +157,9 @@ __global__ __launch_bounds__(1024) void fastq_offsets_scan_kernel(TileSum *__res
   }
   if (threadIdx.x == 0) {
     out_off[n_tiles] = carry_cnt;
-    totals[0] = carry_lines;
-    totals[1] = carry_cnt;
-    totals[2] = (carry_lines + 2) / 4;
+    totals[TOT_LINES] = carry_lines;
+    totals[TOT_TUPLES] = carry_cnt;
+    totals[TOT_SEQS] = (carry_lines + 2) / 4;
   }
 }
 
@@ -187,7 +187,7 @@ __global__ __launch_bounds__(1024) void fastq_offsets_apply_kernel(const TileInf
     uint32_t bad = 0;
     if ((ti.marks >> ((0u - lb) & 3u)) & 1u) bad |= 1u;
     if ((ti.marks >> (4u + ((2u - lb) & 3u))) & 1u) bad |= 2u;
-    if (bad) atomicOr(&flags[0], bad);
+    if (bad) atomicOr(&flags[FLAG_PARSE], bad);
   }
 }
 
@@ -295,7 +295,7 @@ __global__ __launch_bounds__(256) void fastq_check_lengths_kernel(const uint32_t
     }
     wave_sync();   // image and event arrays are rewritten for the next tile
   }
-  if (bad) atomicOr(&flags[0], 4u);
+  if (bad) atomicOr(&flags[FLAG_PARSE], 4u);
 }
 
 // ---------------------------------------------------------------------------
@@ -337,7 +337,7 @@ __global__ __launch_bounds__((ExCfg<NW, BITS>::NT)) void fasta_extract_kernel(
   const uint32_t total = tile_window_list_from<Cfg>(chunk_valid_mask_fasta<Cfg>(s_eol, shape.k, tile0, in.n_bytes, in.n_valid), s_pos, s_scan);
   const uint64_t base = out_off[blockIdx.x];
   if (base + total > out_capacity) {
-    if (threadIdx.x == 0 && total) atomicOr(&flags[1], 1u);
+    if (threadIdx.x == 0 && total) atomicOr(&flags[FLAG_OUT_OVERFLOW], 1u);
     return;
   }
   // records of (key words, id) at a 16-byte aligned address
@@ -589,7 +589,7 @@ __global__ __launch_bounds__((ExCfg<NW, BITS>::NT)) void fastq_extract_kernel(
                                                shape.k, s_pos, s_scan);
   const uint64_t base = out_off[blockIdx.x];
   if (base + total > out_capacity) {
-    if (threadIdx.x == 0 && total) atomicOr(&flags[1], 1u);
+    if (threadIdx.x == 0 && total) atomicOr(&flags[FLAG_OUT_OVERFLOW], 1u);
     return;
   }
   const uint64_t tile0 = (uint64_t)blockIdx.x * Cfg::TILE;
@@ -628,7 +628,7 @@ __global__ __launch_bounds__((ExCfg<NW, BITS>::NT)) void fastq_extract_kernel(
       else if (s_hexcl[j]) rec = tile0 + s_hexcl[j];
       else rec = hdr_base[blockIdx.x];
       const uint64_t rec_off = file_offset + rec - 1u, d = tile0 + pos - (rec - 1u);
-      if (rec == 0 || d > 0xFFFFu) atomicOr(&flags[3], 1u);   // ShortSequenceKmerId increment overflow (sequence.hpp:177-183)
+      if (rec == 0 || d > 0xFFFFu) atomicOr(&flags[FLAG_ID_OVERFLOW], 1u);   // ShortSequenceKmerId increment overflow (sequence.hpp:177-183)
       bool stored = false;
       if constexpr (kRecVec<NW>) {
         if (vec) { store_record_vec<NW>(out_kmers, base + q, key, ((rec_off & 0xFFFFFFFFFFull) << 16) | (d & 0xFFFFull)); stored = true; }
@@ -861,10 +861,10 @@ static kmi_status scan_impl(kmi_ctx *ctx, const uint8_t *bytes_dev, size_t n_byt
   }
   KMI_TRY(launch_tile_offsets(ctx, info, n_tiles, (uint32_t)Cfg::TILE, hdr, base, off));
   if (brk && n_tiles > 0) {
-    // n_seqs under a filter: records that pass / non-empty pieces (totals[2] held lines / 4)
-    KMI_HIP(ctx, hipMemsetAsync(ctx->d_totals + 2, 0, sizeof(uint64_t), ctx->stream));
+    // n_seqs under a filter: records that pass / non-empty pieces (totals[TOT_SEQS] held lines / 4)
+    KMI_HIP(ctx, hipMemsetAsync(ctx->d_totals + TOT_SEQS, 0, sizeof(uint64_t), ctx->stream));
     hipLaunchKernelGGL((fastq_subseq_count_kernel<NW, BITS>), dim3((unsigned)n_tiles), dim3(Cfg::NT), 0, ctx->stream, r->packed,
-                       (const uint32_t *)base, seq_filter == KMI_SEQ_N_SPLIT, (unsigned long long *)(ctx->d_totals + 2));
+                       (const uint32_t *)base, seq_filter == KMI_SEQ_N_SPLIT, (unsigned long long *)(ctx->d_totals + TOT_SEQS));
   }
   if (n_tiles > 0 && check_lengths) {
     ProfScope ps(ctx, "fastq_check", n_bytes);
@@ -878,11 +878,11 @@ static kmi_status scan_impl(kmi_ctx *ctx, const uint8_t *bytes_dev, size_t n_byt
 // totals + FASTQ marker verdict of the last scan
 static kmi_status read_totals(kmi_ctx *ctx, uint64_t *n_tuples, uint64_t *n_seqs) {
   uint32_t flags0 = 0;
-  KMI_HIP(ctx, hipMemcpyAsync(ctx->h_totals, ctx->d_totals, sizeof(uint64_t) * 4, hipMemcpyDeviceToHost, ctx->stream));
+  KMI_HIP(ctx, hipMemcpyAsync(ctx->h_totals, ctx->d_totals, sizeof(uint64_t) * TOT_SCAN_WORDS, hipMemcpyDeviceToHost, ctx->stream));
   KMI_HIP(ctx, hipMemcpyAsync(&flags0, ctx->d_flags, sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
   KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (n_tuples) *n_tuples = ctx->h_totals[1];
-  if (n_seqs) *n_seqs = ctx->h_totals[2];
+  if (n_tuples) *n_tuples = ctx->h_totals[TOT_TUPLES];
+  if (n_seqs) *n_seqs = ctx->h_totals[TOT_SEQS];
   if (flags0 & 1u) return set_err(ctx, KMI_ERR_PARSE, "FASTQ: missing @ on first line of a record");
   if (flags0 & 2u) return set_err(ctx, KMI_ERR_PARSE, "FASTQ: missing + on third line of a record");
   if (flags0 & 4u) return set_err(ctx, KMI_ERR_PARSE, "FASTQ: truncated record? seq and qual differ in length");
@@ -893,7 +893,7 @@ template <int NW, int BITS>
 static kmi_status extract_count_impl(kmi_ctx *ctx, const uint8_t *bytes_dev, size_t n_bytes, KShape shape, uint32_t seq_filter, bool rna,
                                      uint64_t *n_tuples, uint64_t *n_seqs) {
   ScanResult r;
-  KMI_HIP(ctx, hipMemsetAsync(ctx->d_flags, 0, sizeof(uint32_t) * 16, ctx->stream));
+  KMI_HIP(ctx, hipMemsetAsync(ctx->d_flags + FZ_SCAN_0, 0, sizeof(uint32_t) * (FZ_SCAN_1 - FZ_SCAN_0), ctx->stream));
   KMI_TRY((scan_impl<NW, BITS>(ctx, bytes_dev, n_bytes, shape, &r, false, true, seq_filter, rna)));
   return read_totals(ctx, n_tuples, n_seqs);
 }
@@ -909,7 +909,7 @@ static kmi_status extract_run_impl(kmi_ctx *ctx, const kmi_config *cfg, const ui
   uint64_t *ids_at = rec_words ? out_kmers_dev + NW : out_ids_dev;
   const bool want_ids = ids_at != nullptr, want_quals = out_quals_dev != nullptr || rec_words == (uint32_t)NW + 2u;
   ScanResult r;
-  if (!scan_done) KMI_HIP(ctx, hipMemsetAsync(ctx->d_flags, 0, sizeof(uint32_t) * 16, ctx->stream));
+  if (!scan_done) KMI_HIP(ctx, hipMemsetAsync(ctx->d_flags + FZ_SCAN_0, 0, sizeof(uint32_t) * (FZ_SCAN_1 - FZ_SCAN_0), ctx->stream));
   KMI_TRY((scan_impl<NW, BITS>(ctx, bytes_dev, n_bytes, shape, &r, scan_done, true, cfg->seq_filter, is_rna(cfg))));
   if (r.n_tiles > 0) {
     ProfScope ps(ctx, "fastq_extract", n_bytes);
@@ -917,9 +917,9 @@ static kmi_status extract_run_impl(kmi_ctx *ctx, const kmi_config *cfg, const ui
     ReadDesc *reads = nullptr;
     uint64_t n_desc = 0;
     if (want_quals || read_scan) {
-      // one descriptor slot per sequence (totals[2] of the scan), empty until the read's first window fills it
+      // one descriptor slot per sequence (totals[TOT_SEQS] of the scan), empty until the read's first window fills it
       uint64_t n_seq_now = 0;
-      KMI_HIP(ctx, hipMemcpyAsync(&n_seq_now, ctx->d_totals + 2, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+      KMI_HIP(ctx, hipMemcpyAsync(&n_seq_now, ctx->d_totals + TOT_SEQS, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
       KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
       void *pr;
       KMI_TRY(ws_get(ctx, WS_READS, sizeof(ReadDesc) * (n_seq_now + 16), &pr));
@@ -949,17 +949,17 @@ static kmi_status extract_run_impl(kmi_ctx *ctx, const kmi_config *cfg, const ui
       ProfScope pq(ctx, "fastq_quality", n_bytes);
       hipLaunchKernelGGL(fastq_quality_kernel, dim3(2048), dim3(kQualThreads), qual_lds_bytes(shape.k), ctx->stream, bytes_dev,
                          (uint64_t)n_bytes, (const uint32_t *)r.packed.eol, (uint64_t)(r.packed.n_cover / 32), shape.k,
-                         qual_row_bytes(shape.k), (const ReadDesc *)reads, (const uint64_t *)(ctx->d_totals + 2), out_quals_dev,
+                         qual_row_bytes(shape.k), (const ReadDesc *)reads, (const uint64_t *)(ctx->d_totals + TOT_SEQS), out_quals_dev,
                          rec_words == (uint32_t)NW + 2u ? out_kmers_dev + NW + 1 : (uint64_t *)nullptr, rec_words);
     }
   }
   KMI_HIP(ctx, hipGetLastError());
-  uint32_t fl[4] = {0, 0, 0, 0};
+  uint32_t fl[FLAG_ID_OVERFLOW + 1] = {0};   // (the flag words up to the last one read here)
   KMI_HIP(ctx, hipMemcpyAsync(fl, ctx->d_flags, sizeof(fl), hipMemcpyDeviceToHost, ctx->stream));
   KMI_TRY(read_totals(ctx, n_tuples, n_seqs));
-  if (read_scan) read_scan->n_lines = ctx->h_totals[0];
-  if (fl[1]) return set_err(ctx, KMI_ERR_OVERFLOW, "extract: output capacity too small");
-  if (fl[3]) return set_err(ctx, KMI_ERR_OVERFLOW, "ShortSequenceKmerId increment overflow (k-mer more than 65535 bytes into its record)");
+  if (read_scan) read_scan->n_lines = ctx->h_totals[TOT_LINES];
+  if (fl[FLAG_OUT_OVERFLOW]) return set_err(ctx, KMI_ERR_OVERFLOW, "extract: output capacity too small");
+  if (fl[FLAG_ID_OVERFLOW]) return set_err(ctx, KMI_ERR_OVERFLOW, "ShortSequenceKmerId increment overflow (k-mer more than 65535 bytes into its record)");
   return KMI_OK;
 }
 
@@ -967,7 +967,7 @@ template <int NW, int BITS>
 static kmi_status fastq_scan_impl(kmi_ctx *ctx, const uint8_t *bytes_dev, size_t n_bytes, KShape shape, FastqScan *out, bool check_lengths,
                                   bool rna, uint32_t seq_filter) {
   ScanResult r;
-  KMI_HIP(ctx, hipMemsetAsync(ctx->d_flags, 0, sizeof(uint32_t) * 16, ctx->stream));
+  KMI_HIP(ctx, hipMemsetAsync(ctx->d_flags + FZ_SCAN_0, 0, sizeof(uint32_t) * (FZ_SCAN_1 - FZ_SCAN_0), ctx->stream));
   KMI_TRY((scan_impl<NW, BITS>(ctx, bytes_dev, n_bytes, shape, &r, false, check_lengths, seq_filter, rna)));
   out->pk_brk = r.packed.brk;
   out->n_tiles = r.n_tiles; out->line_base = r.line_base; out->tile_off = r.out_off; out->hdr_base = r.hdr_base;
@@ -986,7 +986,7 @@ kmi_status fastq_quality_launch(kmi_ctx *ctx, const uint8_t *bytes_dev, const Fa
   ProfScope pq(ctx, "fastq_quality", sc.n_bytes);
   hipLaunchKernelGGL(fastq_quality_kernel, dim3(2048), dim3(kQualThreads), qual_lds_bytes(k), ctx->stream, bytes_dev, (uint64_t)sc.n_bytes,
                      reinterpret_cast<const uint32_t *>(sc.pk_eol), (uint64_t)(sc.n_cover / 32), k, qual_row_bytes(k), reads,
-                     (const uint64_t *)(ctx->d_totals + 2), out_quals, (uint64_t *)nullptr, 0u);
+                     (const uint64_t *)(ctx->d_totals + TOT_SEQS), out_quals, (uint64_t *)nullptr, 0u);
   KMI_HIP(ctx, hipGetLastError());
   return KMI_OK;
 }
@@ -1019,7 +1019,7 @@ static kmi_status fasta_extract_impl(kmi_ctx *ctx, const kmi_config *cfg, const 
   const uint32_t kstride = rec_words ? rec_words : (uint32_t)NW, istride = rec_words ? rec_words : 1u;
   if (rec_words) out_ids_dev = out_kmers_dev + NW;   // records: the id follows the key words
   FastaScan fs;
-  KMI_HIP(ctx, hipMemsetAsync(ctx->d_flags, 0, sizeof(uint32_t) * 16, ctx->stream));
+  KMI_HIP(ctx, hipMemsetAsync(ctx->d_flags + FZ_SCAN_0, 0, sizeof(uint32_t) * (FZ_SCAN_1 - FZ_SCAN_0), ctx->stream));
   KMI_TRY(fasta_scan(ctx, cfg, bytes_dev, n_bytes, file_offset, out_ids_dev != nullptr, &fs));
   PackedInput in; in.eol = fs.pk_break; in.stream = fs.pk_stream; in.n_bytes = fs.n_chars; in.n_cover = fs.n_cover; in.n_valid = fs.n_valid;
   const uint64_t n_tiles = (fs.n_chars + Cfg::TILE - 1) / Cfg::TILE;
@@ -1046,13 +1046,13 @@ static kmi_status fasta_extract_impl(kmi_ctx *ctx, const kmi_config *cfg, const 
                          ctx->d_flags, kstride, istride, (const uint8_t *)nullptr, (uint64_t)0, false, -1);
   }
   KMI_HIP(ctx, hipGetLastError());
-  uint32_t fl[4] = {0, 0, 0, 0};
+  uint32_t fl[FLAG_ID_OVERFLOW + 1] = {0};   // (the flag words up to the last one read here)
   KMI_HIP(ctx, hipMemcpyAsync(fl, ctx->d_flags, sizeof(fl), hipMemcpyDeviceToHost, ctx->stream));
-  KMI_HIP(ctx, hipMemcpyAsync(ctx->h_totals, ctx->d_totals, sizeof(uint64_t) * 4, hipMemcpyDeviceToHost, ctx->stream));
+  KMI_HIP(ctx, hipMemcpyAsync(ctx->h_totals, ctx->d_totals, sizeof(uint64_t) * TOT_SCAN_WORDS, hipMemcpyDeviceToHost, ctx->stream));
   KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  if (n_tuples) *n_tuples = ctx->h_totals[1];
+  if (n_tuples) *n_tuples = ctx->h_totals[TOT_TUPLES];
   if (n_seqs) *n_seqs = fs.n_seqs;
-  if (fl[1]) return set_err(ctx, KMI_ERR_OVERFLOW, "extract: output capacity too small");
+  if (fl[FLAG_OUT_OVERFLOW]) return set_err(ctx, KMI_ERR_OVERFLOW, "extract: output capacity too small");
   return KMI_OK;
 }
 
@@ -1185,11 +1185,11 @@ uint64_t fastq_batch_end_host(const uint8_t *bytes, size_t n_bytes, uint64_t sta
 }
 kmi_status fastq_batch_end(kmi_ctx *ctx, const uint8_t *bytes_dev, size_t n_bytes, uint64_t start, uint64_t batch, uint64_t *end) {
   if (n_bytes - start <= batch) { *end = n_bytes; return KMI_OK; }
-  hipLaunchKernelGGL(fastq_batch_end_kernel, dim3(1), dim3(64), 0, ctx->stream, bytes_dev, (uint64_t)n_bytes, start, batch, ctx->d_totals + 8);
+  hipLaunchKernelGGL(fastq_batch_end_kernel, dim3(1), dim3(64), 0, ctx->stream, bytes_dev, (uint64_t)n_bytes, start, batch, ctx->d_totals + TOT_BATCH_END);
   KMI_HIP(ctx, hipGetLastError());
-  KMI_HIP(ctx, hipMemcpyAsync(ctx->h_totals + 8, ctx->d_totals + 8, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  KMI_HIP(ctx, hipMemcpyAsync(ctx->h_totals + H_BATCH_END, ctx->d_totals + TOT_BATCH_END, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
   KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  *end = ctx->h_totals[8];
+  *end = ctx->h_totals[H_BATCH_END];
   return KMI_OK;
 }
 

@@ -222,7 +222,7 @@ __global__ __launch_bounds__(1024) void fasta_offsets_reduce_kernel(const FaTile
 }
 
 // in place: sums[b] becomes {state entering block b, characters before it (nseq[0]), record starts before it (nev[0])}
-// totals[0] = sequence characters, totals[2] = records
+// totals[TOT_FA_CHARS] = sequence characters, totals[TOT_SEQS] = records
 __global__ __launch_bounds__(1024) void fasta_offsets_scan_kernel(FaTileSum *__restrict__ sums, uint64_t n_blocks, uint32_t init_state,
                                                                  uint64_t *__restrict__ totals) {
   __shared__ uint32_t s_scanm[1024 / 64 + 2];
@@ -246,7 +246,7 @@ __global__ __launch_bounds__(1024) void fasta_offsets_scan_kernel(FaTileSum *__r
     if (b < n_blocks) { ts.map = st; ts.nseq[0] = rs; ts.nev[0] = re; sums[b] = ts; }
     carry_state = fa_apply(tm, carry_state); carry_seq += t1; carry_ev += t2;
   }
-  if (threadIdx.x == 0) { totals[0] = carry_seq; totals[2] = carry_ev; }
+  if (threadIdx.x == 0) { totals[TOT_FA_CHARS] = carry_seq; totals[TOT_SEQS] = carry_ev; }
 }
 
 __global__ __launch_bounds__(1024) void fasta_offsets_apply_kernel(const FaTileInfo *__restrict__ info, uint64_t n_tiles,
@@ -305,7 +305,7 @@ __global__ __launch_bounds__((FaCfg::NT)) void fasta_compact_kernel(const uint8_
     // characters in the valid range = rank of the first character at or behind byte valid_bytes (partitions only)
     const uint64_t c0 = tile0 + (uint64_t)threadIdx.x * C;
     if (valid_bytes >= c0 && valid_bytes < c0 + C && valid_bytes < n_bytes)
-      totals[3] = rank0 + (uint32_t)__builtin_popcount(r.seq & ((1u << (uint32_t)(valid_bytes - c0)) - 1u));
+      totals[TOT_FA_VALID] = rank0 + (uint32_t)__builtin_popcount(r.seq & ((1u << (uint32_t)(valid_bytes - c0)) - 1u));
   }
   const uint32_t shift0 = (uint32_t)((tb.rank * BITS) & 31u);   // bit phase of the tile inside its first global dword
   // record starts: the first character of the record is the next sequence character = rank_before(position)
@@ -449,13 +449,13 @@ kmi_status fasta_scan(kmi_ctx *ctx, const kmi_config *cfg, const uint8_t *bytes_
                        (const FaTileSum *)sums, base);
   }
   KMI_HIP(ctx, hipGetLastError());
-  KMI_HIP(ctx, hipMemcpyAsync(ctx->h_totals, ctx->d_totals, sizeof(uint64_t) * 4, hipMemcpyDeviceToHost, ctx->stream));
+  KMI_HIP(ctx, hipMemcpyAsync(ctx->h_totals, ctx->d_totals, sizeof(uint64_t) * TOT_SCAN_WORDS, hipMemcpyDeviceToHost, ctx->stream));
   KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   // init_parser: a leading non-header group shifts the sequence indices by one; a partition adds the records before it
   const uint64_t index_shift = part ? (uint64_t)ctx->fa_part.index_shift + ctx->fa_part.records_before
                                     : ((first == '>' || first == ';') ? 0u : 1u);
   const bool drop_n = cfg->seq_filter == KMI_SEQ_N_FILTER;
-  const uint64_t n_rec = ctx->h_totals[2], n_chars_total = ctx->h_totals[0];
+  const uint64_t n_rec = ctx->h_totals[TOT_SEQS], n_chars_total = ctx->h_totals[TOT_FA_CHARS];
   uint64_t *rec_start = nullptr; uint32_t *rec_flag = nullptr;
   if (drop_n) {
     KMI_TRY(ws_get(ctx, WS_PK_NB, (n_rec + 3) * (sizeof(uint64_t) + sizeof(uint32_t)) + 64, &p));
@@ -488,20 +488,20 @@ kmi_status fasta_scan(kmi_ctx *ctx, const kmi_config *cfg, const uint8_t *bytes_
     const uint64_t n_words = (n_chars_total + 31) / 32;
     hipLaunchKernelGGL(fasta_poison_records_kernel, dim3((unsigned)((n_words + 255) / 256)), dim3(256), 0, ctx->stream,
                        (const uint64_t *)rec_start, (const uint32_t *)rec_flag, n_rec, n_words, pk_break);
-    KMI_HIP(ctx, hipMemsetAsync(ctx->d_totals + 1, 0, sizeof(uint64_t), ctx->stream));
+    KMI_HIP(ctx, hipMemsetAsync(ctx->d_totals + TOT_FA_DROPPED, 0, sizeof(uint64_t), ctx->stream));
     hipLaunchKernelGGL(fasta_count_dropped_kernel, dim3(64), dim3(256), 0, ctx->stream, (const uint32_t *)rec_flag, n_rec + 1,
-                       (unsigned long long *)(ctx->d_totals + 1));
-    KMI_HIP(ctx, hipMemcpyAsync(&dropped, ctx->d_totals + 1, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+                       (unsigned long long *)(ctx->d_totals + TOT_FA_DROPPED));
+    KMI_HIP(ctx, hipMemcpyAsync(&dropped, ctx->d_totals + TOT_FA_DROPPED, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
   KMI_HIP(ctx, hipGetLastError());
-  out->n_chars = ctx->h_totals[0];
-  out->n_seqs = ctx->h_totals[2] - dropped;
+  out->n_chars = ctx->h_totals[TOT_FA_CHARS];
+  out->n_seqs = ctx->h_totals[TOT_SEQS] - dropped;
   out->n_valid = out->n_chars;
-  if (valid_bytes < (uint64_t)n_bytes) {   // totals[3] was written by the compaction pass
-    KMI_HIP(ctx, hipMemcpyAsync(ctx->h_totals + 3, ctx->d_totals + 3, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (valid_bytes < (uint64_t)n_bytes) {   // totals[TOT_FA_VALID] was written by the compaction pass
+    KMI_HIP(ctx, hipMemcpyAsync(ctx->h_totals + TOT_FA_VALID, ctx->d_totals + TOT_FA_VALID, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
     KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    out->n_valid = ctx->h_totals[3];
+    out->n_valid = ctx->h_totals[TOT_FA_VALID];
   }
   out->pk_break = (const uint8_t *)pk_break;
   out->pk_stream = (const uint8_t *)pk_stream;

@@ -537,7 +537,7 @@ __global__ __launch_bounds__(kFrThreads) void sk_front_kernel(const uint8_t *__r
       FQ_MARK(6)
     }
     if (!bail && __any(mk_want && mk_ch != mk_want)) { why |= 16u; bail = true; }   // the last batch's markers
-    if (bail) { if (lane == 0) { atomicOr(&flags[9], 4u); atomicOr(&flags[10], why); } }
+    if (bail) { if (lane == 0) { atomicOr(&flags[FLAG_SK_DECLINED], 4u); atomicOr(&flags[FLAG_SK_WHY], why); } }
     wave_sync();
     if (lane == 0) {
       FrRange fr; fr.l0 = (l0 == INF) ? kFrNone : l0; fr.n_lines = (l0 == INF || l0 == kFrNone) ? 0u : n_owned; fr.n_runs = run_count; fr.n_items = item_count;
@@ -554,7 +554,7 @@ __global__ __launch_bounds__(kFrThreads) void sk_front_kernel(const uint8_t *__r
     r = r_next;
   }
 #ifdef KMI_FR_TIMING
-  if (lane == 0) for (int i = 0; i < 8; ++i) atomicAdd(&reinterpret_cast<unsigned long long *>(flags + 48)[i], acc[i]);
+  if (lane == 0) for (int i = 0; i < 8; ++i) atomicAdd(&reinterpret_cast<unsigned long long *>(flags + FLAG_CLOCKS)[i], acc[i]);
 #endif
 #ifdef KMI_FR_LEAVE
   if (lane == 0 && blockIdx.x * (uint32_t)kFrWaves + wv < kFrTimingWaves) {
@@ -583,7 +583,7 @@ __global__ __launch_bounds__(kFrScThreads, 2) void sk_scatter_rows_kernel(const 
   // One record format, whether the records go to this GPU's back end or through an exchange: word 1 keeps its 18 bucket bits as
   // the owner will read them, and bits 61..63 are zero (kmi_superkmer.h: no record's word 1 is all ones).
   // (launched before the host has looked at the front end's verdict: a front end that gave up has left tables nobody may walk)
-  if (__hip_atomic_load(&flags[9], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
+  if (__hip_atomic_load(&flags[FLAG_SK_DECLINED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
   // One lane per run; the round's items are brought into LDS ONCE (sixteen bytes at a time from each run's list) and everything
   // after that -- bucket counts, the bucket sort of (run, item) references, the copy-out that assembles the records -- reads
   // them there. (Kept in registers and re-read from global memory for the copy-out, the items made this kernel wait on the
@@ -760,7 +760,7 @@ __global__ __launch_bounds__(1024) void sk_front_verify_kernel(const FrRange *__
   lds_barrier();
   if (threadIdx.x == 0) {
     totals[0] = carry; totals[1] = runs; totals[2] = its;
-    if (s_bad) atomicOr(&flags[9], 4u);
+    if (s_bad) atomicOr(&flags[FLAG_SK_DECLINED], 4u);
   }
   // runs per group (what a scatter workgroup will walk)
   const uint32_t groups = (n_ranges + ranges_per_group - 1) / ranges_per_group;

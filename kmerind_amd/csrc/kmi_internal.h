@@ -69,6 +69,88 @@ enum WsSlot {
   WS_NUM_SLOTS
 };
 
+// ---- the device scalars of a context: who owns which word. Every index into d_flags, d_totals and h_totals goes through these names
+// (a word a kernel gets as `base + NAME` it indexes from 0: sk_front_verify_kernel's three totals at TOT_FRONT).
+// d_flags: FLAG_NUM_WORDS dwords. Kernels raise them with atomics; the host reads a word and clears it where it acts on it.
+// Words 0 .. 15 live within ONE call: whoever raises one is read (and answered) before that call returns, so every scan and the
+// one-pass front end start by clearing all sixteen ([FZ_SCAN_0, FZ_SCAN_1), [FZ_FRONT_0, FZ_FRONT_1)) -- the words of the reduce
+// and of the tuple kernels among them (FLAG_PASS_LIMIT, FLAG_ID_OVERFLOW, FLAG_REDUCE_CHECK, FLAG_OUT_OVERFLOW), on purpose.
+enum FlagWord : uint32_t {
+  FLAG_PARSE = 0,           // FASTQ record rules, bits 1 / 2 / 4 / 8: the scan kernels and fastq_list_kernel raise them; fastq_scan clears; read_totals, fastq_length_verdict read
+  FLAG_OUT_OVERFLOW = 1,    // the extract kernels: more tuples than the output holds; cleared with the scan's words; extract_run reads
+  FLAG_PASS_LIMIT = 2,      // bucket_reduce_kernel / sk_reduce_kernel: a bucket went over the pass limit; adopt_tmp reads and clears
+  FLAG_ID_OVERFLOW = 3,     // the tuple kernels: a ShortSequenceKmerId increment overflowed; the position builds read and clear
+  FLAG_REDUCE_CHECK = 8,    // bucket_reduce_kernel: "a bucket overflowed, later buckets check"; reduce_and_adopt clears before the launch
+  FLAG_SK_DECLINED = 9,     // super-k-mer front ends: not this path's input (sk_minimizer, fasta_runs: 1 / 2 a capacity; sk_front, sk_front_verify: 4);
+                            // sk_zero_kernel (one-pass) or a fill (general) clears; the front ends read, sk_scatter_rows_kernel reads on the device
+  FLAG_SK_WHY = 10,         // sk_front_kernel: the reasons it declined (KMI_FRONT_DEBUG prints them); cleared with FLAG_SK_DECLINED
+  FLAG_FRONT_QUEUE = 12,    // sk_front_kernel: the next byte range to hand out; sk_zero_kernel clears before the launch
+  FLAG_SK_LEVEL0 = 16,      // sk_reduce_kernel: buckets that ended at level 0 .. 8 (9 words); sk_back_end clears and reads (the next build's hint)
+  FLAG_SK_LEVEL_END = 34,   // (words 25 .. 33 are cleared with the votes and unused)
+  FLAG_SK_ROOM = 34,        // sk_scatter_fine_slack_lines_kernel: a fine bucket outgrew its room; sk_zero_kernel clears; sk_back_end reads
+  FLAG_LOOKUP_NPASS = 36,   // bucket_lookup_kernel: the largest pass count of the call's buckets; lookup clears and reads
+  FLAG_LOOKUP_OVER = 37,    // bucket_lookup_kernel: a bucket went over the pass limit; lookup clears and reads
+  FLAG_REDUCE_QUEUE = 40,   // sk_reduce_kernel: the next fine bucket to hand out (41 .. 47 spare, cleared with it); sk_back_end clears
+  FLAG_REDUCE_QUEUE_END = 48,
+  FLAG_CLOCKS = 48,         // timing builds (KMI_FR_TIMING, KMI_SK_TIMING): 8 64-bit wave clocks; the reports read and clear them
+  FLAG_NUM_WORDS = 64,
+  // the flag ranges cleared in one go: by the fill that starts every scan (kmi_extract.hip) [FZ_SCAN_0, FZ_SCAN_1); by sk_zero_kernel
+  // the one-pass front end's [FZ_FRONT_0, FZ_FRONT_1), the slack back end's [FZ_BACK_0, FZ_BACK_1) and [FZ_BACK_2, FZ_BACK_3)
+  FZ_SCAN_0 = 0, FZ_SCAN_1 = 16, FZ_FRONT_0 = 0, FZ_FRONT_1 = 16, FZ_BACK_0 = 16, FZ_BACK_1 = 35, FZ_BACK_2 = 40, FZ_BACK_3 = 48
+};
+static_assert(FZ_SCAN_0 == FZ_FRONT_0 && FZ_SCAN_1 == FZ_FRONT_1 && FLAG_REDUCE_CHECK < FZ_SCAN_1,
+              "a scan and the one-pass front end clear the same per-call words, and nothing of the back end or the lookup (below)");
+static_assert(FZ_FRONT_0 <= FLAG_PARSE && FLAG_SK_DECLINED < FZ_FRONT_1 && FLAG_SK_WHY < FZ_FRONT_1 && FLAG_FRONT_QUEUE < FZ_FRONT_1,
+              "the front end's launch clears the parse flags, its verdict words and its range queue");
+static_assert(FZ_FRONT_1 <= FLAG_SK_LEVEL0, "... and none of the back end's words");
+static_assert(FZ_BACK_0 == FLAG_SK_LEVEL0 && FZ_BACK_1 == FLAG_SK_ROOM + 1 && FLAG_SK_LEVEL_END == FLAG_SK_ROOM,
+              "the back end's first range: the level votes and the room flag, nothing else");
+static_assert(FZ_BACK_1 <= FLAG_LOOKUP_NPASS && FLAG_LOOKUP_OVER == FLAG_LOOKUP_NPASS + 1 && FLAG_LOOKUP_OVER < FZ_BACK_2,
+              "the lookup's two words lie together (one fill, one read-back) and outside both ranges");
+static_assert(FZ_BACK_2 == FLAG_REDUCE_QUEUE && FZ_BACK_3 == FLAG_REDUCE_QUEUE_END && FLAG_REDUCE_QUEUE_END <= FLAG_CLOCKS,
+              "the back end's second range: the queue word and its spare words, not the clocks");
+static_assert(FLAG_SK_LEVEL0 + 9 <= FLAG_SK_LEVEL_END && FLAG_CLOCKS + 16 <= FLAG_NUM_WORDS, "the votes and the clocks fit");
+
+// d_totals: 16 64-bit words, then 256 coarse-bucket totals. h_totals (pinned): their mirror, then the mailbox.
+enum TotalWord : uint32_t {
+  TOT_LINES = 0,            // FASTQ scan: lines. The scan kernels write words 0 .. 2; read_totals reads them (h_totals mirrors words 0 .. 3 under these names)
+  TOT_FA_CHARS = 0,         // FASTA scan: sequence characters (the same word: a context scans one format at a time); fasta_scan reads
+  TOT_TUPLES = 1,           // FASTQ scan: k-mer windows
+  TOT_FA_DROPPED = 1,       // FASTA scan: records dropped by the filter (the same word: a FASTA scan has no tuple total); fasta_scan clears and reads
+  TOT_SEQS = 2,             // sequences / records; the filter count and the quality pass rewrite and read it on the device
+  TOT_FA_VALID = 3,         // FASTA compaction: characters whose byte lies in the valid range
+  TOT_SCAN_WORDS = 4,       // (words 0 .. 3 come back in one copy: read_totals, fasta_scan)
+  TOT_ENTRIES = 4,          // bucket_offsets_kernel: entries of the index after a reduce or an erase; adopt_tmp and the erase read (read_total)
+  TOT_RESULTS = 5,          // bucket_offsets_kernel: results of a count / find; the queries read (read_total)
+  TOT_SK_KMERS = 6,        // k-mers of a super-k-mer build: sk_front / fasta_runs / sk_recv_hist add; sk_zero_kernel or a fill clears; the front ends read
+  TOT_UPDATED = 7,          // update kernels: entries changed; update clears and reads
+  TOT_BATCH_END = 8,        // fastq_batch_end_kernel writes; fastq_batch_end reads
+  TOT_FRONT = 12,           // sk_front_verify_kernel: lines, runs, items (3 words); sk_front_fast reads
+  TOT_COARSE = 16,          // fine_totals_kernel: [256] coarse totals of the fine-offset scan (launch_fine_offsets)
+  TOT_NUM_WORDS = 16 + 256
+};
+// one owner per total word: the named words in ascending order with nothing between two of them unaccounted for (9 .. 11 and 15 are free)
+static_assert(TOT_FA_VALID + 1 == TOT_SCAN_WORDS && TOT_SCAN_WORDS == TOT_ENTRIES && TOT_ENTRIES + 1 == TOT_RESULTS &&
+              TOT_RESULTS + 1 == TOT_SK_KMERS && TOT_SK_KMERS + 1 == TOT_UPDATED && TOT_UPDATED + 1 == TOT_BATCH_END &&
+              TOT_BATCH_END < TOT_FRONT && TOT_FRONT + 3 <= TOT_COARSE && TOT_COARSE + 256 == TOT_NUM_WORDS, "one owner per total word");
+// h_totals: words 0 .. 15 mirror d_totals under the TotalWord names (read_totals, fasta_scan, read_total copy word for word);
+// the words below are the host's own
+enum HostWord : uint32_t {
+  H_BATCH_END = 8,          // mirror of TOT_BATCH_END (read at once, behind a synchronisation)
+  H_SK_LEVELS = 8,          // sk_back_end: the 9 level votes, words 8 .. 12 (queued, read after adopt_tmp's synchronisation). Shares word 8 with
+                            // H_BATCH_END: both are read before the host thread queues anything else into them
+  H_SK_ROOM = 14,           // sk_back_end: FLAG_SK_ROOM
+  H_MAIL = 16,              // sk_front_fast's read-backs, one synchronisation for all of them:
+  H_MAIL_CNT = H_MAIL,             // [256] records and [256] starts of the coarse groups
+  H_MAIL_DECLINED = H_MAIL + 512,  // FLAG_SK_DECLINED
+  H_MAIL_FRONT = H_MAIL + 513,     // TOT_FRONT's three words
+  H_MAIL_KMERS = H_MAIL + 516,     // TOT_SK_KMERS
+  H_NUM_WORDS = 16 + 1024
+};
+static_assert(H_BATCH_END == (uint32_t)TOT_BATCH_END && H_SK_LEVELS > (uint32_t)TOT_RESULTS && H_SK_LEVELS + 5 <= H_SK_ROOM &&
+              H_SK_ROOM < H_MAIL && H_MAIL == (uint32_t)TOT_COARSE && H_MAIL_KMERS < H_NUM_WORDS,
+              "the read-backs of a build overlap neither each other nor the mirrored totals a build reads (entries, results)");
+
 struct ProfRec {
   const char *name;
   hipEvent_t e0, e1;
@@ -88,9 +170,9 @@ struct kmi_ctx {
   hipStream_t stream = nullptr;
   std::string err;
   struct Buf { void *p = nullptr; size_t cap = 0; } ws[kmi::WS_NUM_SLOTS];
-  uint32_t *d_flags = nullptr;   // [64] error / overflow flags, pass-structure votes (16..33), sk_reduce's queue word (40; 41..47 spare)
+  uint32_t *d_flags = nullptr;   // [FLAG_NUM_WORDS] error / overflow flags, votes, queue words: enum FlagWord names every word and its owner
   uint32_t n_cus = 0;            // compute units of the device (grids of persistent workgroups)
-  uint64_t *d_totals = nullptr;  // [16] small device scalars + [256] coarse-bucket totals of the fine-offset scan
+  uint64_t *d_totals = nullptr;  // [16] small device scalars + [256] coarse-bucket totals of the fine-offset scan (enum TotalWord)
   hipEvent_t ev_mail = nullptr;  // marks "the read-backs queued so far have landed" (waited for instead of the whole stream)
   // a build from HOST bytes whose copy has not been queued yet (kmi_index_build_host): the one-pass front end queues it in chunks
   // on copy_stream and starts the byte ranges of a chunk behind it; every other reader of the input calls feed_flush first
@@ -106,7 +188,7 @@ struct kmi_ctx {
   bool host_overlap = true;      // KMI_HOST_OVERLAP=0: one copy on the build's stream, then the build
   size_t host_overlap_min = (size_t)64 << 20;   // ... and inputs below this many bytes always go that way (KMI_HOST_OVERLAP_MIN; tests lower it)
   size_t feed_min_chunk = (size_t)8 << 20;      // a copy chunk is not split further below this (KMI_FEED_MIN_CHUNK)
-  uint64_t *h_totals = nullptr;  // pinned mirror: 16 words of totals, then 1024 words for larger read-backs (one synchronisation for all of them)
+  uint64_t *h_totals = nullptr;  // pinned mirror: 16 words of totals, then 1024 words for larger read-backs (one synchronisation for all of them; enum HostWord)
   bool prof = false;
   std::vector<kmi::ProfRec> prof_pending;
   std::vector<kmi::ProfAgg> prof_agg;

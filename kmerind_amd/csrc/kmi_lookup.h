@@ -158,15 +158,15 @@ __global__ __launch_bounds__(kProfThreads) void read_profile_reduce_kernel(const
 
 static kmi_status lookup_begin(kmi_ctx *ctx) {
   ctx->lookup_npass = 0;
-  // d_flags[36]: the largest pass count of the call's buckets; [37]: a bucket went over the pass limit (words of their own: the scan of
+  // FLAG_LOOKUP_NPASS: the largest pass count of the call's buckets; FLAG_LOOKUP_OVER: a bucket went over the pass limit (words of their own: the scan of
   // every batch of a profile clears the low flag words)
-  KMI_HIP(ctx, hipMemsetAsync(ctx->d_flags + 36, 0, 2 * sizeof(uint32_t), ctx->stream));
+  KMI_HIP(ctx, hipMemsetAsync(ctx->d_flags + FLAG_LOOKUP_NPASS, 0, 2 * sizeof(uint32_t), ctx->stream));
   return KMI_OK;
 }
 // waits for the call's work; the pass-limit verdict, reported as the other queries report it
 static kmi_status lookup_end(kmi_ctx *ctx) {
   uint32_t f[2] = {0, 0};
-  KMI_HIP(ctx, hipMemcpyAsync(f, ctx->d_flags + 36, sizeof(f), hipMemcpyDeviceToHost, ctx->stream));
+  KMI_HIP(ctx, hipMemcpyAsync(f, ctx->d_flags + FLAG_LOOKUP_NPASS, sizeof(f), hipMemcpyDeviceToHost, ctx->stream));
   KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   ctx->lookup_npass = f[0];
   if (f[1]) {
@@ -192,7 +192,7 @@ static kmi_status lookup_records_impl(kmi_index *idx, const uint64_t *recs_dev, 
     ProfScope ps(ctx, "bucket_lookup", n);
     hipLaunchKernelGGL((bucket_lookup_kernel<NW>), dim3(kNumFine), dim3(QTabCfg<NW>::NT), 0, ctx->stream, (const uint64_t *)part.keys,
                        (const uint64_t *)part.fine_off, (const uint64_t *)idx->keys, (const uint32_t *)idx->vals, (const uint64_t *)idx->bucket_off,
-                       (const uint32_t *)idx->bucket_cnt, cap, counts_dev, ctx->d_flags + 37, ctx->d_flags + 36);
+                       (const uint32_t *)idx->bucket_cnt, cap, counts_dev, ctx->d_flags + FLAG_LOOKUP_OVER, ctx->d_flags + FLAG_LOOKUP_NPASS);
   }
   KMI_HIP(ctx, hipGetLastError());
   return KMI_OK;

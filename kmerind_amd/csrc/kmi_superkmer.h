@@ -159,7 +159,7 @@ __global__ __launch_bounds__(256) void fasta_runs_kernel(const uint32_t *__restr
     const uint32_t wsum = wave_reduce_sum(nwin);
     if (lane == 0) {
       ent_cnt[t] = total < stride ? total : stride;
-      if (total > stride) atomicOr(&flags[9], 1u);   // more runs than the tile's slots: the caller takes the k-mer path
+      if (total > stride) atomicOr(&flags[FLAG_SK_DECLINED], 1u);   // more runs than the tile's slots: the caller takes the k-mer path
       if (wsum) atomicAdd(n_windows, (unsigned long long)wsum);
     }
   }
@@ -294,7 +294,7 @@ __global__ __launch_bounds__(kSkThreads, 2) void sk_minimizer_kernel(PackedInput
         ++cnt;
       }
     }
-    if (cnt > (uint32_t)CAP + 1u) { atomicOr(&flags[9], 1u); cnt = 1; }
+    if (cnt > (uint32_t)CAP + 1u) { atomicOr(&flags[FLAG_SK_DECLINED], 1u); cnt = 1; }
     cnt = cnt ? cnt - 1u : 0u;   // real items: slots 1 .. cnt
     // items in their final form (window offset | (n - 1) << 7 | bucket bits << 12 | two further hash bits << 30) + the coarse counts
     {
@@ -311,7 +311,7 @@ __global__ __launch_bounds__(kSkThreads, 2) void sk_minimizer_kernel(PackedInput
     uint32_t total;
     const uint32_t ex = block_exclusive_scan<uint32_t>(cnt, s_scan, &total);
     if (item_base + round_base + total > item_end) {   // uniform
-      if (threadIdx.x == 0) atomicOr(&flags[9], 2u);
+      if (threadIdx.x == 0) atomicOr(&flags[FLAG_SK_DECLINED], 2u);
     } else {
       uint32_t *dst = items + item_base + round_base + ex;
       for (uint32_t j = 0; j < cnt; ++j) dst[j] = s_list[(j + 1u) * NT + threadIdx.x];
@@ -515,7 +515,7 @@ __global__ __launch_bounds__(1024) void sk_fine_count_kernel(const uint64_t *__r
 // mean share of c's records, which the front end counted), and a workgroup appends its tile's records of a fine bucket behind
 // what the bucket holds so far -- global atomics on the bucket's counter -- instead of writing to offsets a histogram pass
 // (sk_fine_count: one more read of all records) would have prepared. It also adds up the k-mers per fine bucket (the reduce's
-// output ranges). A bucket that outgrows its room raises flags[34]: the caller then takes the exact path.
+// output ranges). A bucket that outgrows its room raises flags[FLAG_SK_ROOM]: the caller then takes the exact path.
 // Bucket b's records end up at fine_region[b >> 7] + (b & 127) * fine_cap[b >> 7], fine_cnt[b] of them (pad records included),
 // in no particular order.
 // The pass writes WHOLE LINES. A tile's records of a fine bucket written where the bucket's counter stood are runs of about 32
@@ -571,7 +571,7 @@ __global__ __launch_bounds__(kPartThreads) void sk_scatter_fine_slack_lines_kern
   // room for `n` records (a multiple of 8) of fine bucket f: the position inside the region, or ~0 when the bucket has outgrown it
   auto take = [&](uint32_t f, uint32_t n) -> uint64_t {
     const uint32_t at = atomicAdd(&fine_cnt[c * NB + f], n);
-    if ((uint64_t)at + n > (uint64_t)cap) { atomicOr(&flags[34], 1u); return ~0ull; }
+    if ((uint64_t)at + n > (uint64_t)cap) { atomicOr(&flags[FLAG_SK_ROOM], 1u); return ~0ull; }
     return region + (uint64_t)f * cap + at;
   };
   load_tile(b);
@@ -1272,16 +1272,16 @@ __global__ __launch_bounds__(KMI_SK_NT, KMI_SK_MIN_WAVES) void sk_reduce_kernel(
       vm_landed();
       if (threadIdx.x == 0) { s_ctl[C_DIST] = 0; s_ctl[C_OVF] = 0; s_ctl[C_T1N] = 0; s_ctl[C_OVN] = 0; }
       if (lost) {
-        // Overflow: this pass is split -- straight to the level most buckets of this build ended at (flags[16 + L] counts the
+        // Overflow: this pass is split -- straight to the level most buckets of this build ended at (flags[FLAG_SK_LEVEL0 + L] counts the
         // buckets that finished with L filter bits) instead of one bit at a time. The table is emptied without being read.
         for (uint32_t i = threadIdx.x; i < (uint32_t)T::S2; i += T::NT) { s_tk[i] = kEmptyKey; s_tv[i] = 0; }
         if (threadIdx.x == 0) {
           s_ctl[C_SPC] = 0; s_ctl[C_SPS] = 0;
-          if (fbits >= 18u) atomicOr(&flags[2], 1u);   // 3 record bits + 15 hash bits: 2^18 tables did not hold the bucket
+          if (fbits >= 18u) atomicOr(&flags[FLAG_PASS_LIMIT], 1u);   // 3 record bits + 15 hash bits: 2^18 tables did not hold the bucket
           else {
             uint32_t best = 0, best_n = 0;
             for (uint32_t l = 0; l <= 8u; ++l) {
-              const uint32_t c = __hip_atomic_load(&flags[16 + l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+              const uint32_t c = __hip_atomic_load(&flags[FLAG_SK_LEVEL0 + l], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
               if (c > best_n) { best_n = c; best = l; }
             }
             uint32_t target = best > fbits ? best : fbits + 1u;
@@ -1361,7 +1361,7 @@ __global__ __launch_bounds__(KMI_SK_NT, KMI_SK_MIN_WAVES) void sk_reduce_kernel(
     }
     if (threadIdx.x == 0) {
       out_cnt[b] = s_ctl[C_EMIT];
-      if (n_rec && (s_ctl[C_LVL] || start_bits)) atomicAdd(&flags[16 + (s_ctl[C_LVL] > 8u ? 8u : s_ctl[C_LVL])], 1u);
+      if (n_rec && (s_ctl[C_LVL] || start_bits)) atomicAdd(&flags[FLAG_SK_LEVEL0 + (s_ctl[C_LVL] > 8u ? 8u : s_ctl[C_LVL])], 1u);
     }
     lds_barrier();   // everyone has left the pass loop (the next bucket's set-up rewrites the stack words)
     const uint32_t b2 = __builtin_amdgcn_readfirstlane(s_ctl[C_NEXT + par]);
@@ -1370,7 +1370,7 @@ __global__ __launch_bounds__(KMI_SK_NT, KMI_SK_MIN_WAVES) void sk_reduce_kernel(
     TQ_MARK(6)
   }
 #ifdef KMI_SK_TIMING
-  if (lane == 0) for (int i = 0; i < 8; ++i) atomicAdd(&reinterpret_cast<unsigned long long *>(flags + 48)[i], acc[i]);
+  if (lane == 0) for (int i = 0; i < 8; ++i) atomicAdd(&reinterpret_cast<unsigned long long *>(flags + FLAG_CLOCKS)[i], acc[i]);
 #endif
 }
 

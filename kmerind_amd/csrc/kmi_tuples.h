@@ -161,7 +161,7 @@ __global__ __launch_bounds__((ExCfg<NW, BITS>::NT)) void tuple_scatter_kernel(Pa
             else if (s_hexcl[cj]) rec = tile0 + s_hexcl[cj];
             else rec = hdr_base[tile];
             const uint64_t rec_off = file_offset + rec - 1u, d = tile0 + pos - (rec - 1u);
-            if (rec == 0 || d > 0xFFFFu) atomicOr(&flags[3], 1u);   // ShortSequenceKmerId increment overflow (sequence.hpp:177-183)
+            if (rec == 0 || d > 0xFFFFu) atomicOr(&flags[FLAG_ID_OVERFLOW], 1u);   // ShortSequenceKmerId increment overflow (sequence.hpp:177-183)
             v[j][0] = ((rec_off & 0xFFFFFFFFFFull) << 16) | (d & 0xFFFFull);
           }
           if (VW > 1) v[j][VW - 1] = in_q ? (uint64_t)__float_as_uint(in_q[base + q]) : 0ull;

@@ -106,15 +106,15 @@ static kmi_status update_pairs_impl(kmi_index *idx, uint64_t *recs_dev, size_t n
   }
   Partitioned part;
   KMI_TRY((partition_impl<NW, BITS, 1>(ctx, &idx->cfg, idx->shape, recs_dev, n, true, WS_KEYS_A, WS_KEYS_B, &part, idx->layout_w)));
-  KMI_HIP(ctx, hipMemsetAsync(ctx->d_totals + 7, 0, sizeof(uint64_t), ctx->stream));
+  KMI_HIP(ctx, hipMemsetAsync(ctx->d_totals + TOT_UPDATED, 0, sizeof(uint64_t), ctx->stream));
   {
     ProfScope ps(ctx, "bucket_update", n);
     hipLaunchKernelGGL((bucket_update_kernel<NW>), dim3(kNumFine), dim3(DbgCfg<NW>::NT), 0, ctx->stream, (const uint64_t *)idx->keys,
                        (const uint64_t *)idx->bucket_off, idx->vals, (const uint64_t *)part.keys, (const uint64_t *)part.fine_off, op,
-                       (unsigned long long *)(ctx->d_totals + 7));
+                       (unsigned long long *)(ctx->d_totals + TOT_UPDATED));
   }
   KMI_HIP(ctx, hipGetLastError());
-  KMI_HIP(ctx, hipMemcpyAsync(n_updated, ctx->d_totals + 7, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  KMI_HIP(ctx, hipMemcpyAsync(n_updated, ctx->d_totals + TOT_UPDATED, sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
   KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return KMI_OK;
 }
