@@ -443,9 +443,21 @@ class Index {
       if (fd && std::atoi(fd) != 0) ::kmerind::check(ctx, kmi_comm_create(ctx, nullptr, &rccl));
     }
   }
+  // A second index in `sibling`'s context, over its communicator (no reference counterpart: there two maps over one mxx::comm
+  // simply coexist). compare() and combine() take two indexes of ONE context, so the second operand is made this way. The
+  // sibling owns the context and the communicator and must outlive this index.
+  struct same_context_t {};
+  Index(const Index &sibling, same_context_t) : comm(sibling.comm), ctx(sibling.ctx), rccl(sibling.rccl), owns_ctx(false) {
+    cfg = detail::make_config<MapType>(KMI_FMT_FASTQ);
+    ::kmerind::check(ctx, kmi_index_create(ctx, &cfg, &idx));
+    if (MapType::saturating && MapType::index_kind == KMI_INDEX_COUNT) ::kmerind::check(ctx, kmi_index_set_saturating(idx, 1));
+  }
   Index(const Index &) = delete;
   Index &operator=(const Index &) = delete;
-  virtual ~Index() { if (rccl) kmi_comm_destroy(rccl); if (idx) kmi_index_destroy(idx); if (ctx) kmi_ctx_destroy(ctx); }
+  virtual ~Index() {
+    if (idx) kmi_index_destroy(idx);
+    if (owns_ctx) { if (rccl) kmi_comm_destroy(rccl); if (ctx) kmi_ctx_destroy(ctx); }
+  }
 
   // Index::insert (kmer_index.hpp:200-225): vector<Kmer>, or the map's own tuples. For the counting maps a tuple's value is
   // ADDED to the key's count (reduction_unordered_map::local_insert, distributed_unordered_map.hpp:1603-1618); for the
@@ -737,6 +749,25 @@ class Index {
     return (size_t)n;
   }
 
+  // ---- two count indexes of one context (Index(sibling, same_context_t{})) joined on the device.
+  // compare: the eight words of kmi_index_overlap for this index (a) and other (b), over all ranks (collective when size() > 1).
+  kmi_index_overlap compare(Index const &other) const {
+    static_assert(MapType::index_kind == KMI_INDEX_COUNT, "compare() is a member of the count index");
+    kmi_index_overlap o{};
+    if (rccl) ::kmerind::check(ctx, kmi_index_compare_dist_host(idx, other.idx, rccl, &o));
+    else ::kmerind::check(ctx, kmi_index_compare(idx, other.idx, &o));
+    return o;
+  }
+  // combine: this index := this index (op) other, op = KMI_COMBINE_*. Local on every rank (nothing is exchanged: two indexes built
+  // over the same communicator hold a key on the same rank, so the union of the ranks' combined shares is the combined map);
+  // returns this rank's new size.
+  size_t combine(Index const &other, uint32_t op) {
+    static_assert(MapType::index_kind == KMI_INDEX_COUNT, "combine() is a member of the count index");
+    uint64_t n = 0;
+    ::kmerind::check(ctx, kmi_index_combine(idx, other.idx, op, &n));
+    return (size_t)n;
+  }
+
   kmi_ctx *context() const { return ctx; }
   const kmi_config &config() const { return cfg; }
 
@@ -896,6 +927,7 @@ class Index {
   kmi_ctx *ctx = nullptr;
   kmi_index *idx = nullptr;
   kmi_comm *rccl = nullptr;
+  bool owns_ctx = true;   // false: made with same_context_t, the sibling destroys the context and the communicator
   MapView view{};
 };
 

@@ -100,7 +100,9 @@ kmi_status kmi_ctx_reset_hints(kmi_ctx *ctx);
  * and 3: calls that reached hipMalloc; 4: blocks taken from the process-wide cache instead; 5: pointer-jumping rounds, 6: exchanges
  * and 7: bytes this rank sent in the context's last kmi_dbg_compact_dist_host; 8: the largest number of passes a bucket needed in
  * the context's last kmi_index_lookup_* / kmi_index_profile_reads_* (1 when every bucket's entries fit one table; 0: no bucket was
- * looked at); 9: the entry count of the fullest bucket the context's last kmi_index_retain_counts met (0: the index was empty) */
+ * looked at); 9: the entry count of the fullest bucket the context's last kmi_index_retain_counts met (0: the index was empty);
+ * 10: the largest number of passes a bucket needed in the context's last kmi_index_compare* / kmi_index_combine (0: no bucket
+ * was looked at) */
 kmi_status kmi_ctx_debug_counter(const kmi_ctx *ctx, uint32_t which, uint64_t *value);
 /* A destroyed context leaves its large device blocks (workspace, spare index arrays: >= 1 MB each, 96 GB / 64 blocks at most) in a
  * process-wide cache per device, where the next context of that device finds them: its first build then does not wait for
@@ -518,6 +520,73 @@ kmi_status kmi_index_spectrum_dev (kmi_index *idx, uint32_t n_bins, uint64_t *hi
 kmi_status kmi_index_spectrum_host(kmi_index *idx, uint32_t n_bins, uint64_t *hist,     kmi_spectrum_totals *totals /* may be NULL */);
 kmi_status kmi_index_spectrum_dist_host(kmi_index *idx, kmi_comm *comm, uint32_t n_bins, uint64_t *hist, kmi_spectrum_totals *totals /* may be NULL */);
 kmi_status kmi_index_retain_counts(kmi_index *idx, uint32_t lo, uint32_t hi, uint64_t *n_erased /* may be NULL */);
+
+/* ---- two count indexes compared and combined (no counterpart in the reference, where this is to_vector() of one map, count() or
+ * find() in the other and a host loop; KMC's `simple` operations and Jellyfish `merge` are the precedents)
+ * Two indexes of one k-mer shape and one internal layout hold a key in the same bucket, so the join is bucket against bucket on
+ * the device: nothing is partitioned and no key travels to the host.
+ *
+ * Membership is by key. A key whose stored count is 0 is present (update with ASSIGN or MIN can store a 0). "Shared" means the
+ * same stored key; both indexes hold keys after the same InputTransform because their configurations must agree (Operands).
+ *
+ * compare: neither index's entries change. The eight words give
+ *   Jaccard = n_shared / (n_a + n_b - n_shared), containment of a in b = n_shared / n_a,
+ *   weighted Jaccard = sum_min_shared / (sum_a + sum_b - sum_min_shared);
+ * the struct stays integer so that it can be tested exactly. compare(a, a) is allowed and gives n_shared == n_a.
+ *
+ * combine: a becomes the result, b's entries are unchanged. With ca / cb the stored counts (an absent key counting 0 where the
+ * row says so):
+ *   KMI_COMBINE_UNION_ADD        keys in a or in b             ca + cb
+ *   KMI_COMBINE_UNION_MAX        keys in a or in b             max(ca, cb)
+ *   KMI_COMBINE_INTERSECT_MIN    keys in both                  min(ca, cb)
+ *   KMI_COMBINE_INTERSECT_ADD    keys in both                  ca + cb
+ *   KMI_COMBINE_INTERSECT_LEFT   keys in both                  ca
+ *   KMI_COMBINE_SUBTRACT_KEYS    keys in a and not in b        ca
+ *   KMI_COMBINE_SUBTRACT_COUNTS  keys in a with ca > cb        ca - cb      (absent from b: cb = 0, so a stored 0 of a leaves)
+ * ca + cb follows a's reducer: it wraps by default and stops at 2^32 - 1 after kmi_index_set_saturating(a, 1). The result lies in
+ * fresh arrays of exactly its size, in a's layout family; owner ranks, saturation setting and configuration are unchanged, and
+ * every later operation works on a as on any index, also when nothing survived. The order of the entries inside the result is
+ * not specified. On any error a still holds what it held. An unknown op or a == b gives KMI_ERR_INVALID. *n_entries = the entries
+ * of a afterwards. (A call that cannot change a -- a union with an empty b, anything else on an empty a, SUBTRACT_KEYS with an
+ * empty b -- leaves a's arrays where they are.)
+ *
+ * Operands. Anything outside these rules gives KMI_ERR_INVALID with both indexes untouched: both are count indexes (a position
+ * index is refused), both belong to the same context, both have the same k, alphabet and strand model, and both have the same
+ * kmi_index_owner_ranks.
+ *
+ * Shapes and forms. Every shape a count index takes (one to four words; 2-, 3- and 4-bit alphabets), dense and sparse indexes
+ * alike, either layout held by either operand. The join reads a sparse operand as it is. An operand's INTERNAL FORM may change
+ * while its entries do not: when the layouts differ one operand is brought to the other's -- for combine that is a, for compare
+ * the smaller one -- and the two unions bring both operands to the dense form first, because the merge reads bucket b as
+ * [offset b, offset b + 1).
+ *
+ * Empty cases. An index that has never been filled counts as empty. Empty against anything is well defined: compare gives zeros
+ * but for the other operand's n_ and sum_ words, combine the table's rows.
+ *
+ * Passes. A bucket of b whose entries do not fit one table is worked on in passes, as in the lookup; KMI_ERR_OVERFLOW when a
+ * bucket exceeds the pass limit. KMI_LOOKUP_CAP shrinks this table too. kmi_ctx_debug_counter 10 gives the largest number of
+ * passes a bucket needed in the context's last compare or combine, 0 when no bucket was looked at.
+ *
+ * Ranks. combine needs no _dist form: every key lives on exactly one rank under either ownership rule, so two indexes built over
+ * the same communicator with the same owner rule combine share by share, and the union of the shares is the combined map (the
+ * equal owner_ranks test guards the rule). compare_dist_host is collective: the eight words summed over the ranks. A rank whose
+ * local join fails does not leave its peers waiting: they return KMI_ERR_PEER. Operand errors are every rank's alike and return
+ * before anything collective starts. Works over a one-rank communicator.
+ *
+ * Completion. All three calls are complete on return. */
+typedef struct {
+  uint64_t n_a, n_b;            /* entries of a and of b (= kmi_index_local_size) */
+  uint64_t n_shared;            /* keys stored in both */
+  uint64_t sum_a, sum_b;        /* sum of all stored counts, 64-bit, never clamped */
+  uint64_t sum_a_shared;        /* sum of a's counts over the shared keys */
+  uint64_t sum_b_shared;        /* ... of b's */
+  uint64_t sum_min_shared;      /* sum over the shared keys of min(count in a, count in b) */
+} kmi_index_overlap;            /* 64 bytes */
+enum { KMI_COMBINE_UNION_ADD = 0, KMI_COMBINE_UNION_MAX = 1, KMI_COMBINE_INTERSECT_MIN = 2, KMI_COMBINE_INTERSECT_ADD = 3,
+       KMI_COMBINE_INTERSECT_LEFT = 4, KMI_COMBINE_SUBTRACT_KEYS = 5, KMI_COMBINE_SUBTRACT_COUNTS = 6 };
+kmi_status kmi_index_compare(kmi_index *a, kmi_index *b, kmi_index_overlap *out);
+kmi_status kmi_index_compare_dist_host(kmi_index *a, kmi_index *b, kmi_comm *comm, kmi_index_overlap *out);
+kmi_status kmi_index_combine(kmi_index *a, kmi_index *b, uint32_t op, uint64_t *n_entries /* of a afterwards; may be NULL */);
 
 /* ---- a count index over 2, 4 or 8 ranks through exchanged super-k-mers ---------------
  * The reference's distributed insert sends every k-mer to KeyToRank(k-mer) (8 bytes per k-mer over the wire,

@@ -54,6 +54,16 @@ class SpectrumTotals(C.Structure):
 SPECTRUM_MAX_BINS = 65536
 
 
+class IndexOverlap(C.Structure):
+    _fields_ = [("n_a", C.c_uint64), ("n_b", C.c_uint64), ("n_shared", C.c_uint64), ("sum_a", C.c_uint64), ("sum_b", C.c_uint64),
+                ("sum_a_shared", C.c_uint64), ("sum_b_shared", C.c_uint64), ("sum_min_shared", C.c_uint64)]
+
+
+# KMI_COMBINE_*
+COMBINE_OPS = {"union_add": 0, "union_max": 1, "intersect_min": 2, "intersect_add": 3, "intersect_left": 4, "subtract_keys": 5,
+               "subtract_counts": 6}
+
+
 class KernelTime(C.Structure):
     _fields_ = [("name", C.c_char_p), ("total_ms", C.c_double), ("launches", C.c_uint64), ("units", C.c_uint64)]
 
@@ -159,6 +169,9 @@ SIGNATURES = {
     "kmi_index_spectrum_host": (C.c_int, [_P, _u32, _P, C.POINTER(SpectrumTotals)]),
     "kmi_index_spectrum_dist_host": (C.c_int, [_P, _P, _u32, _P, C.POINTER(SpectrumTotals)]),
     "kmi_index_retain_counts": (C.c_int, [_P, _u32, _u32, C.POINTER(_u64)]),
+    "kmi_index_compare": (C.c_int, [_P, _P, C.POINTER(IndexOverlap)]),
+    "kmi_index_compare_dist_host": (C.c_int, [_P, _P, _P, C.POINTER(IndexOverlap)]),
+    "kmi_index_combine": (C.c_int, [_P, _P, _u32, C.POINTER(_u64)]),
     "kmi_index_sk_produce_dev": (C.c_int, [_P, _P, _sz, _u32, _P, _sz, C.POINTER(_P), C.POINTER(_u64), _P, C.POINTER(C.c_int)]),
     "kmi_index_sk_consume_dev": (C.c_int, [_P, _P, _sz, _u32]),
     "kmi_route_owner_dev": (C.c_int, [_P, _CFG, _P, _sz, _u32, _P, _P]),

@@ -390,6 +390,41 @@ class CountIndex:
         self.ctx.check(lib.kmi_index_retain_counts(self.h, lo, hi, C.byref(n)))
         return n.value
 
+    # ---- two count indexes compared and combined on the device (kmi_index_compare* / kmi_index_combine)
+    @staticmethod
+    def _overlap(o):
+        d = {name: int(getattr(o, name)) for name, _ in L.IndexOverlap._fields_}
+
+        def ratio(num, den):
+            return num / den if den else 0.0
+        d["jaccard"] = ratio(d["n_shared"], d["n_a"] + d["n_b"] - d["n_shared"])
+        d["containment_a"] = ratio(d["n_shared"], d["n_a"])
+        d["containment_b"] = ratio(d["n_shared"], d["n_b"])
+        d["weighted_jaccard"] = ratio(d["sum_min_shared"], d["sum_a"] + d["sum_b"] - d["sum_min_shared"])
+        return d
+
+    def compare(self, other, comm=None):
+        """the overlap of this index (a) and `other` (b): a dict of the eight words of kmi_index_overlap plus jaccard,
+        containment_a, containment_b and weighted_jaccard as floats (0.0 where the denominator is 0). With a communicator
+        (anything with a kmi_comm handle `h`) the words are summed over the ranks: collective."""
+        o = L.IndexOverlap()
+        if comm is None:
+            self.ctx.check(lib.kmi_index_compare(self.h, other.h, C.byref(o)))
+        else:
+            self.ctx.check(lib.kmi_index_compare_dist_host(self.h, other.h, comm.h, C.byref(o)))
+        return self._overlap(o)
+
+    def combine(self, other, op):
+        """this index := this index (op) other, on the device; op is one of union_add, union_max, intersect_min, intersect_add,
+        intersect_left, subtract_keys, subtract_counts -> the new size"""
+        if isinstance(op, str):
+            if op not in L.COMBINE_OPS:
+                raise ValueError("combine: unknown op %r" % (op,))
+            op = L.COMBINE_OPS[op]
+        n = C.c_uint64()
+        self.ctx.check(lib.kmi_index_combine(self.h, other.h, op, C.byref(n)))
+        return n.value
+
 
 class PositionIndex(CountIndex):
     """bliss::index::kmer::PositionIndex<unordered_multimap> on one rank (kmer_index.hpp:402-403):

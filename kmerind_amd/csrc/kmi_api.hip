@@ -288,6 +288,7 @@ kmi_status kmi_ctx_debug_counter(const kmi_ctx *ctx, uint32_t which, uint64_t *v
     case 7: *value = ctx->unitig_dist_bytes; return KMI_OK;
     case 8: *value = ctx->lookup_npass; return KMI_OK;
     case 9: *value = ctx->retain_fullest; return KMI_OK;
+    case 10: *value = ctx->setops_npass; return KMI_OK;
     default: return KMI_ERR_INVALID;
   }
 }

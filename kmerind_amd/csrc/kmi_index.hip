@@ -2238,7 +2238,10 @@ __global__ __launch_bounds__((TabCfg<NW>::NT)) void bucket_merge_kernel(const ui
                                                                        const uint64_t *__restrict__ old_keys, const uint32_t *__restrict__ old_vals,
                                                                        const uint64_t *__restrict__ old_off, uint64_t *__restrict__ tmp_keys,
                                                                        uint32_t *__restrict__ tmp_vals, uint32_t *__restrict__ out_cnt,
-                                                                       uint32_t *__restrict__ flags, bool sat = false) {
+                                                                       uint32_t *__restrict__ flags, bool sat = false, bool take_max = false,
+                                                                       uint32_t *__restrict__ max_npass = nullptr) {
+  // take_max (kmi_setops.h, UNION_MAX): a key's count is the largest of its contributions instead of their sum
+  // max_npass (kmi_setops.h): the largest pass count of the call's buckets
   KMI_TABLE_LDS(NW)
   const uint32_t b = blockIdx.x;
   const uint64_t ob = old_off ? old_off[b] : 0ull, oe = old_off ? old_off[b + 1] : 0ull;
@@ -2257,8 +2260,9 @@ __global__ __launch_bounds__((TabCfg<NW>::NT)) void bucket_merge_kernel(const ui
           const uint32_t h = place_hash<NW>(k);
           if (pass_of(h, npass) != pass) return;
           int s = table_upsert<NW>(tab, k, h);
-          if (s >= 0) count_add(&tab.vals[s], vals[i], sat);
-          else if (s == -2) count_add(tab.special, vals[i], sat);
+          uint32_t *c = s >= 0 ? &tab.vals[s] : (s == -2 ? tab.special : nullptr);
+          if (!c) return;
+          if (take_max) atomicMax(c, vals[i]); else count_add(c, vals[i], sat);
         });
       };
       add(old_keys, old_vals, ob, oe);
@@ -2290,7 +2294,10 @@ __global__ __launch_bounds__((TabCfg<NW>::NT)) void bucket_merge_kernel(const ui
     if (npass > kMaxPasses) { if (threadIdx.x == 0) { atomicOr(&flags[FLAG_PASS_LIMIT], 1u); *s_out = 0; } lds_barrier(); break; }
     lds_barrier();
   }
-  if (threadIdx.x == 0) out_cnt[b] = *s_out;
+  if (threadIdx.x == 0) {
+    out_cnt[b] = *s_out;
+    if (max_npass) atomicMax(max_npass, npass > kMaxPasses ? kMaxPasses : npass);
+  }
 }
 
 // Weighted insert: reduction_unordered_map::local_insert with the caller's value (distributed_unordered_map.hpp:1603-1618,
@@ -3668,6 +3675,7 @@ static kmi_status merge_impl(kmi_index *idx, uint32_t nparts, const uint64_t *ke
 #include "kmi_update.h"
 #include "kmi_lookup.h"
 #include "kmi_spectrum.h"
+#include "kmi_setops.h"
 
 struct kmi_comm;
 static kmi_status dist_state(kmi_index *idx, kmi_comm *comm, uint64_t *holders, uint64_t *owner_p, uint64_t *owner_any);
@@ -5370,6 +5378,49 @@ kmi_status kmi_index_retain_counts(kmi_index *idx, uint32_t lo, uint32_t hi, uin
   if (!idx->has_data || idx->n_entries == 0) return KMI_OK;
   KMI_HIP(ctx, hipSetDevice(ctx->device));
   return index_retain_counts(idx, lo, hi, n_erased);
+}
+
+// ---- two count indexes compared and combined (kmi_setops.h)
+kmi_status kmi_index_compare(kmi_index *a, kmi_index *b, kmi_index_overlap *out) {
+  if (!a || !b || !out) return KMI_ERR_INVALID;
+  kmi_ctx *ctx = a->ctx;
+  memset(out, 0, sizeof(*out));
+  KMI_TRY(setops_check(a, b, "compare"));
+  ctx->setops_npass = 0;
+  KMI_HIP(ctx, hipSetDevice(ctx->device));
+  const kmi_status st = index_compare(a, b, out);
+  if (st != KMI_OK) memset(out, 0, sizeof(*out));
+  return st;
+}
+
+kmi_status kmi_index_compare_dist_host(kmi_index *a, kmi_index *b, kmi_comm *comm, kmi_index_overlap *out) {
+  KMI_TRY(dist_check(a, comm));
+  // (argument errors are every rank's alike: nothing collective has started)
+  if (!b || !out) return KMI_ERR_INVALID;
+  memset(out, 0, sizeof(*out));
+  KMI_TRY(setops_check(a, b, "compare"));
+  kmi_index_overlap mine_words{};
+  const kmi_status mine = kmi_index_compare(a, b, &mine_words);
+  KMI_TRY(dist_agree(comm, mine));   // a rank whose join failed does not leave the others in the all-reduce
+  static_assert(sizeof(kmi_index_overlap) == 8 * sizeof(uint64_t), "eight words");
+  uint64_t words[8];
+  memcpy(words, &mine_words, sizeof(words));
+  KMI_TRY(kmi::comm_allreduce_sum(comm, words, 8));
+  memcpy(out, words, sizeof(words));
+  return KMI_OK;
+}
+
+kmi_status kmi_index_combine(kmi_index *a, kmi_index *b, uint32_t op, uint64_t *n_entries) {
+  if (!a || !b) return KMI_ERR_INVALID;
+  kmi_ctx *ctx = a->ctx;
+  if (n_entries) *n_entries = a->has_data ? a->n_entries : 0;
+  KMI_TRY(setops_check(a, b, "combine"));
+  if (op > (uint32_t)KMI_COMBINE_SUBTRACT_COUNTS) return set_err(ctx, KMI_ERR_INVALID, "combine: unknown op");
+  if (a == b) return set_err(ctx, KMI_ERR_INVALID, "combine: a and b are the same index");
+  KMI_HIP(ctx, hipSetDevice(ctx->device));
+  const kmi_status st = index_combine(a, b, op);
+  if (n_entries) *n_entries = a->has_data ? a->n_entries : 0;
+  return st;
 }
 
 }  // extern "C"

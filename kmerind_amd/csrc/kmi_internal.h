@@ -222,6 +222,7 @@ struct kmi_ctx {
   size_t profile_batch = (size_t)256 << 20;   // input bytes of a batch of kmi_index_profile_reads_* (KMI_PROFILE_BATCH)
   uint64_t lookup_npass = 0;     // the largest pass count a bucket used in the last lookup / profile (kmi_ctx_debug_counter 8)
   uint64_t retain_fullest = 0;   // entries of the fullest bucket the last kmi_index_retain_counts met (kmi_ctx_debug_counter 9)
+  uint64_t setops_npass = 0;     // the largest pass count a bucket used in the last kmi_index_compare / kmi_index_combine (kmi_ctx_debug_counter 10)
   int fa_left_carry = -1;        // de Bruijn tuples of a FASTA block (kmi_dbg_build_fasta_range_dist_host): the raw byte of the sequence
                                  // character before the block's first one, the in-edge of its first window; -1: none
 };
