@@ -184,7 +184,8 @@ __global__ __launch_bounds__((DbgCfg<NW>::NT)) void dbg_accumulate_kernel(const 
 
 // The same sums from SUPER-K-MER records (the build through the count index's own front and back end, dbg_build_superkmer below).
 // A record (kmi_superkmer.h) is a stretch of a read: k + n - 1 bases as complement codes, base i at bits 2 i, in whichever of its
-// two orientations is the smaller number, + the base before its first and behind its last k-mer (kRecEdgeShift). Its k-mer j has the
+// two orientations is the smaller number, + the base before its first and behind its last k-mer (kRecEdgeShift) and which of the
+// two orientations it is (kRecFlipShift). Its k-mer j has the
 // neighbours base j - 1 and base j + k of the SAME record -- the two outside bases for j = 0 and j = n - 1 -- so nothing but the
 // record is read: edge_iterator.hpp:84-177 without a tuple per k-mer. The records of fine bucket b are still where the count
 // build's scatter pass left them; the nodes of b are the (dense) entries [idx_off[b], idx_off[b + 1]) of the node index, which the
@@ -194,6 +195,7 @@ __global__ __launch_bounds__((DbgCfg<NW>::NT)) void dbg_accumulate_kernel(const 
 // unit marks of a wavefront's batch: 64 records of up to 15 units + slack. An edge record holds sk_nmax_of(k) - kSkEdgeWindows k-mers:
 // 18 (9 units) for k = 31, but 29 (15 units) for k <= 20 -- a batch of such records (poly-A reads) wrote its marks past the wavefront's share
 constexpr int kSkEdgeOwn = 64 * 16;
+static_assert(64 * ((32 - (int)kSkEdgeWindows + 1) / 2) <= kSkEdgeOwn, "a wavefront's unit marks: 64 records of the most k-mers an edge record holds");
 __global__ __launch_bounds__((DbgCfg<1>::NT)) void sk_edges_accumulate_kernel(const uint64_t *__restrict__ idx_keys, const uint64_t *__restrict__ idx_off,
                                                                            const uint64_t *__restrict__ recs, const uint64_t *__restrict__ rec_off,
                                                                            const uint64_t *__restrict__ fine_region, const uint32_t *__restrict__ fine_cap,
@@ -296,7 +298,8 @@ __global__ __launch_bounds__((DbgCfg<1>::NT)) void sk_edges_accumulate_kernel(co
           const bool two = act && j + 1u < rn;
           // complement code of base i of the record (bases sit below bit 96: words a0..a2)
           auto cc = [&](uint32_t i) -> uint32_t { const uint32_t w = i >= 32u ? a2 : (i >= 16u ? a1 : a0); return (w >> (2u * (i & 15u))) & 3u; };
-          // k-mer j: 2 k bits from bit 2 j (j is even, at most 16: the window starts in word 0 or 1) -- sk_reduce's cut, on 32-bit registers
+          // k-mer j: 2 k bits from bit 2 j (j is even, at most 28 -- a record of 29 k-mers at k <= 20: the window starts in word 0 or, for
+          // j >= 16, in word 1, which w1sel selects) -- sk_reduce's cut, on 32-bit registers
           const bool w1sel = j >= 16u;
           const uint32_t bit = (2u * j) & 31u;
           const uint32_t b0 = w1sel ? a1 : a0, b1 = w1sel ? a2 : a1, b2 = w1sel ? (a3 & 0u) : a2;   // (nothing of word 3 is a base)
@@ -318,7 +321,10 @@ __global__ __launch_bounds__((DbgCfg<1>::NT)) void sk_edges_accumulate_kernel(co
           const uint32_t out_a = (j + 1u < rn) ? 4u - c_jk : rout;
           const uint32_t in_c = 4u - (rc_lo & 3u);                                         // base j
           const uint32_t out_c = (j + 2u < rn) ? 4u - cc(j + k + 1u) : rout;
-          const bool rev_a = rc < fw, rev_c = rc2 < fw2;                                   // the node is the reverse strand: edges change sides, complemented
+          // the node is the reverse strand: edges change sides, complemented. A k-mer that equals its reverse complement takes its
+          // edges as the read has them: turned back if the record travels reverse-complemented
+          const bool rflip = (a3 >> (kRecFlipShift - 32)) & 1u;
+          const bool rev_a = rc < fw || (rflip && rc == fw), rev_c = rc2 < fw2 || (rflip && rc2 == fw2);
           const uint64_t ka = rev_a ? rc : fw, kc = rev_c ? rc2 : fw2;
           const uint32_t ia = rev_a ? (out_a ? 5u - out_a : 0u) : in_a, oa = rev_a ? (in_a ? 5u - in_a : 0u) : out_a;
           const uint32_t ic = rev_c ? (out_c ? 5u - out_c : 0u) : in_c, oc = rev_c ? (in_c ? 5u - in_c : 0u) : out_c;

@@ -579,9 +579,11 @@ __global__ __launch_bounds__(kFrScThreads, 2) void sk_scatter_rows_kernel(const 
                                                                          const uint64_t *__restrict__ wg_off, uint64_t *__restrict__ out, uint32_t lp,
                                                                          const uint32_t *__restrict__ flags, uint32_t edges = 0u) {
   // edges: the record's two outside bases (sk_front_kernel) go to bits 32..37 of word 1 as 1 + base code (A C G T = 0..3 in the
-  // record's own orientation; 0: the read ends there) -- see sk_edge_codes
+  // record's own orientation; 0: the read ends there), and bit 61 says that the record is the reverse complement of the read's
+  // stretch (kRecFlipShift) -- see sk_edge_codes
   // One record format, whether the records go to this GPU's back end or through an exchange: word 1 keeps its 18 bucket bits as
-  // the owner will read them, and bits 61..63 are zero (kmi_superkmer.h: no record's word 1 is all ones).
+  // the owner will read them, and bits 61..63 are zero -- bits 62 and 63 in an edge record (kmi_superkmer.h: no record's word 1 is
+  // all ones).
   // (launched before the host has looked at the front end's verdict: a front end that gave up has left tables nobody may walk)
   if (__hip_atomic_load(&flags[FLAG_SK_DECLINED], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) return;
   // One lane per run; the round's items are brought into LDS ONCE (sixteen bytes at a time from each run's list) and everything
@@ -722,7 +724,7 @@ __global__ __launch_bounds__(kFrScThreads, 2) void sk_scatter_rows_kernel(const 
         const uint32_t lc = wfirst ? 1u + (3u - cc(wfirst - 1u)) : (runx & 7u);
         const uint32_t rc = wfirst + n1 + 1u < (uint32_t)s_runw[rl] ? 1u + (3u - cc(after)) : (runx >> 3);
         const uint32_t left = flipped ? (rc ? 5u - rc : 0u) : lc, right = flipped ? (lc ? 5u - lc : 0u) : rc;
-        w1 |= (uint64_t)(left | (right << 3)) << kRecEdgeShift;
+        w1 |= ((uint64_t)(left | (right << 3)) << kRecEdgeShift) | ((uint64_t)(flipped ? 1u : 0u) << kRecFlipShift);
       }
       reinterpret_cast<ulonglong2 *>(out)[s_gbase[h27 >> 19] + s] = make_ulonglong2(w0, w1);
     }

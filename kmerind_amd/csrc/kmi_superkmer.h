@@ -27,15 +27,17 @@
 namespace kmi {
 
 // record (16 bytes): word 0 = bases 0..31 of the complement-stream slice, word 1 = bases 32..50 (38 bits) | (n - 1) << 38 |
-// bucket bits << 43 (18 bits: coarse 8 | fine 7 | sub 3, most significant first). Bits 61..63 of word 1 are ZERO in every record,
-// whichever front end wrote it: that is why an all-ones word 1 -- kSkPadW1 here, W1_INIT of sk_reduce_kernel's record table --
-// can never be a record's.
+// bucket bits << 43 (18 bits: coarse 8 | fine 7 | sub 3, most significant first). Bits 62 and 63 of word 1 are ZERO in every record,
+// whichever front end wrote it (bit 61 too, but for the edge records below): that is why an all-ones word 1 -- kSkPadW1 here,
+// W1_INIT of sk_reduce_kernel's record table -- can never be a record's.
 constexpr int kRecNShift = 38, kRecHashShift = 43;
 constexpr uint64_t kSkPadW1 = ~0ull;   // second word of a PAD record (sk_scatter_fine_slack_lines_kernel); readers of a fine bucket skip it
 // records of the de Bruijn node build: three windows fewer per record (sk_nmax_of - kSkEdgeWindows), and the two outside bases where
 // the last three bases would be: bits 32..34 the base before the first k-mer, 35..37 the base behind the last one, each 1 + its code
-// (A C G T = 0..3 in the record's orientation), 0 = the read ends there
-constexpr int kRecEdgeShift = 32;
+// (A C G T = 0..3 in the record's orientation), 0 = the read ends there. Bit 61: the record is the reverse complement of its stretch
+// of the read. Nothing else can tell for a k-mer that equals its own reverse complement (even k), and its node takes the edges as
+// the READ has them (the tuple path and the reference flip the edges only of a k-mer that is larger than its reverse complement).
+constexpr int kRecEdgeShift = 32, kRecFlipShift = 61;
 constexpr uint32_t kSkEdgeWindows = 3;
 __device__ __forceinline__ uint32_t rec_hash18(uint64_t w1) { return (uint32_t)(w1 >> kRecHashShift) & 0x3ffffu; }
 __device__ __forceinline__ uint32_t rec_fine_sub(uint64_t w1) { return (rec_hash18(w1) >> 3) & 127u; }   // fine bucket inside its coarse bucket
@@ -842,7 +844,7 @@ __global__ __launch_bounds__(KMI_SK_NT, KMI_SK_MIN_WAVES) void sk_reduce_kernel(
   };
   using T = SkTab2<OWN_>;
   constexpr int NWAVES = T::NWAVES;
-  constexpr uint64_t W1_INIT = ~0ull;   // never a record's second word (bits 61..63 of a record's are zero: see the record layout)
+  constexpr uint64_t W1_INIT = ~0ull;   // never a record's second word (bits 62 and 63 of a record's are zero: see the record layout)
   enum { C_DIST = 0, C_OVF = 1, C_SPC = 2, C_SPS = 3, C_EMIT = 4, C_SP = 5, C_OVN = 6, C_T1N = 8, C_LVL = 9, C_NEXT = 10 /* and 11 */ };
   __shared__ uint64_t s_tk[T::S2];
   __shared__ uint32_t s_tv[T::S2];

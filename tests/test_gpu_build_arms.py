@@ -16,7 +16,9 @@ k = 17, 21, 23, 31, 32: the four window widths, and sk_reduce's instantiation fo
 Not reached here: the general front end exceeding its item capacity on a real input (sk_minimizer_kernel raising FLAG_SK_DECLINED),
 behind which the k-mer pipeline runs. Under KMI_FRONT=general, k = 17 and 31, 300 reads of 150 bases that are one base, AC, ACGT,
 TGCA, TTGGCCAA repeated or descending runs (TTTGA TTGCA TGCCA ...), and 40 reads of 5000 bases of A and of AC, all stayed within
-the capacities; tests/test_gpu_dist_clayer.py reaches the hand-over behind that arm through KMI_SK_DBG=7."""
+the capacities; tests/test_gpu_dist_clayer.py reaches the hand-over behind that arm through KMI_SK_DBG=7.
+The low-complexity inputs of the node build's edge records (one base, tandem repeats, the last reads of the buffer) are in
+tests/test_gpu_debruijn_records.py."""
 import ctypes as C
 import os
 import socket

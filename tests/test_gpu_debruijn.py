@@ -1,6 +1,7 @@
 """GPU parity of the de Bruijn node build (kmi_dbg_*, test/test/debruijn/ of the reference) against the oracle's
 restatement: parser tuples bit for bit; nodes compared in the orientation of the smaller strand (the reference keeps
-whichever strand arrived first, the library the smaller one -- include/kmerind_hip.h)."""
+whichever strand arrived first, the library the smaller one -- include/kmerind_hip.h).
+The low-complexity cases of the build through super-k-mer edge records are in tests/test_gpu_debruijn_records.py."""
 import os
 
 import numpy as np

@@ -29,18 +29,19 @@ def test_copies_of_a_record_in_the_same_step(copies, n_reads):
     c.close()
 
 
-def _crowd(k, n, seed):
+def _crowd(k, n, seed, w=W, copies=2, fastq=_fastq):
     """n distinct reads of 18 random bases, the m-mer of smallest order hash, 18 random bases, each present twice in a shuffled order
-    (some twins side by side, most apart): one record of 19 k-mers per read, all in ONE fine bucket"""
-    m = k - W + 1
+    (some twins side by side, most apart): one record of 19 k-mers per read, all in ONE fine bucket. (w: for another window width,
+    w - 1 bases on either side and w k-mers per read; copies: how often each read is present; fastq: the writer of the file)"""
+    m = k - w + 1
     mm = _smallest_mmer(m)
     rng = np.random.default_rng(seed)
     fixed = np.array([(mm >> (2 * (m - 1 - j))) & 3 for j in range(m)], dtype=np.uint8)
-    codes = np.concatenate([rng.integers(0, 4, (n, 18), dtype=np.uint8), np.broadcast_to(fixed, (n, m)), rng.integers(0, 4, (n, 18), dtype=np.uint8)], axis=1)
+    codes = np.concatenate([rng.integers(0, 4, (n, w - 1), dtype=np.uint8), np.broadcast_to(fixed, (n, m)), rng.integers(0, 4, (n, w - 1), dtype=np.uint8)], axis=1)
     assert np.unique(codes, axis=0).shape[0] == n
-    mins = _minimizers(codes, k)
-    assert mins.shape == (n, 19) and (mins == np.uint64(mm)).all()
-    return _fastq(codes[rng.permutation(np.repeat(np.arange(n), 2))])
+    mins = _minimizers(codes, k, w)
+    assert mins.shape == (n, w) and (mins == np.uint64(mm)).all()
+    return fastq(codes[rng.permutation(np.repeat(np.arange(n), copies))])
 
 
 @pytest.mark.parametrize("k,strand", [(31, "canonical"), (32, "single")])

@@ -45,9 +45,10 @@ def _smallest_mmer(m):
             return c
 
 
-def _minimizers(codes, k):
-    """codes: (reads, length) base codes; the canonical m-mer of smallest order hash of every k-mer -> (reads, k-mers)"""
-    m = k - W + 1
+def _minimizers(codes, k, w=W):
+    """codes: (reads, length) base codes; the canonical m-mer of smallest order hash of every k-mer -> (reads, k-mers); w: the
+    windows per k-mer of that k (sk_window_of)"""
+    m = k - w + 1
     n, length = codes.shape
     npos = length - m + 1
     f = np.zeros((n, npos), dtype=np.uint64)
@@ -58,7 +59,7 @@ def _minimizers(codes, k):
     canon = np.minimum(f, r)
     hashes = _order_hash(canon)
     nk = length - k + 1
-    best = np.stack([hashes[:, p:p + nk] for p in range(W)]).argmin(axis=0)        # (the hash is a bijection: no ties between m-mers)
+    best = np.stack([hashes[:, p:p + nk] for p in range(w)]).argmin(axis=0)        # (the hash is a bijection: no ties between m-mers)
     return np.take_along_axis(canon, best + np.arange(nk)[None, :], axis=1)
 
 
