@@ -39,6 +39,22 @@ def test_kmer_shape_matches_reference_sizes():
         K.Context.shape(K.make_config(200, "DNA"))
 
 
+def test_kmer_shape_of_the_widest_instantiations():
+    """first and last k of every (n_words, bits) pair beyond the ones above, the two 3-bit edges (k = 43: a character across bit
+    128; k = 64: 192 bits, no pad), and the first k past four words per alphabet"""
+    import kmerind_amd as K
+    want = {(97, "DNA"): (4, 194, 25), (128, "DNA"): (4, 256, 32), (65, "DNA5"): (4, 195, 25), (85, "DNA5"): (4, 255, 32),
+            (17, "DNA16"): (2, 68, 9), (32, "DNA16"): (2, 128, 16), (33, "DNA16"): (3, 132, 17), (48, "DNA16"): (3, 192, 24),
+            (49, "DNA16"): (4, 196, 25), (64, "DNA16"): (4, 256, 32), (43, "DNA5"): (3, 129, 17), (64, "DNA5"): (3, 192, 24)}
+    for (k, alpha), shape in want.items():
+        assert K.Context.shape(K.make_config(k, alpha)) == shape, (k, alpha)
+        s = orc.kspec(k, {"DNA": orc.DNA, "DNA5": orc.DNA5, "DNA16": orc.DNA16}[alpha])
+        assert (s.n_words, s.n_bits, s.n_bytes) == shape, (k, alpha)
+    for k, alpha in ((129, "DNA"), (86, "DNA5"), (65, "DNA16")):
+        with pytest.raises(ValueError):
+            K.Context.shape(K.make_config(k, alpha))
+
+
 def test_no_cpu_fallback():
     import torch
     if torch.cuda.is_available():

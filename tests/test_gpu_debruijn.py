@@ -62,25 +62,33 @@ def test_nodes_build_insert_find(ctx, k, alpha):
     s = orc.kspec(k, ALPHA[alpha])
     cfg = K.make_config(k, alpha)
     data = _with_n(bytes(K.synth_fastq(seed=k, genome_len=4000, n_reads=1500)), k)
+    data2 = _with_n(bytes(K.synth_fastq(seed=k, genome_len=4000, n_reads=700, first_read=4000)), k + 1)
+    absent = orc.extract(s, bytes(K.synth_fastq(seed=77, genome_len=60000, n_reads=20)), orc.FASTQ)["kmers"]
+    check_nodes_build_insert_find(ctx, s, cfg, data, data2, absent, seed=k)
+
+
+def check_nodes_build_insert_find(ctx, s, cfg, data, data2, absent, seed):
+    """parse and build of `data`, insert(tuples) of `data2`, find / count / clear: shared with test_gpu_shape_matrix.py"""
+    import kmerind_amd as K
     ok, oe = orc.dbg_parse(s, data)
     om = orc.DbgMap(s)
     om.insert(ok, oe)
     g = K.DeBruijnNodes(ctx, cfg)
+    gk, ge = g.parse(data)
+    assert gk.shape == ok.shape and (gk == ok).all() and (ge == oe).all()
     g.build(data)
     assert g.local_size() == om.size()
     assert (_nodes(*g.to_vector()) == _nodes(*om.export(canonical=True))).all()
     # a second batch through insert(tuples), reversed so that other strands arrive first in the oracle's map
-    data2 = _with_n(bytes(K.synth_fastq(seed=k, genome_len=4000, n_reads=700, first_read=4000)), k + 1)
     k2, e2 = orc.dbg_parse(s, data2)
     om.insert(k2[::-1].copy(), e2[::-1].copy())
     g.insert(k2, e2)
     assert g.local_size() == om.size()
     assert (_nodes(*g.to_vector()) == _nodes(*om.export(canonical=True))).all()
     # find: present under either strand (with repeats), absent
-    rng = np.random.default_rng(k)
+    rng = np.random.default_rng(seed)
     present = ok[rng.integers(0, ok.shape[0], size=2000)]
     flipped = orc.revcomp(s, present[:700])
-    absent = orc.extract(s, bytes(K.synth_fastq(seed=77, genome_len=60000, n_reads=20)), orc.FASTQ)["kmers"]
     q = np.concatenate([present, flipped, absent, present[:40]])
     assert (_nodes(*g.find(q)) == _nodes(*om.find(q, canonical=True))).all()
     ck, cc = g.count(q)
@@ -101,16 +109,23 @@ def test_erase_nodes(ctx, k, alpha):
     s = orc.kspec(k, ALPHA[alpha])
     cfg = K.make_config(k, alpha)
     data = _with_n(bytes(K.synth_fastq(seed=3 * k, genome_len=5000, n_reads=1800)), k)
+    data2 = _with_n(bytes(K.synth_fastq(seed=3 * k, genome_len=5000, n_reads=600, first_read=2500)), k + 1)
+    absent = orc.extract(s, bytes(K.synth_fastq(seed=91, genome_len=50000, n_reads=15)), orc.FASTQ)["kmers"]
+    check_erase_nodes(ctx, s, cfg, data, data2, absent, seed=k)
+
+
+def check_erase_nodes(ctx, s, cfg, data, data2, absent, seed):
+    """shared with test_gpu_shape_matrix.py"""
+    import kmerind_amd as K
     ok, oe = orc.dbg_parse(s, data)
     om = orc.DbgMap(s)
     om.insert(ok, oe)
     g = K.DeBruijnNodes(ctx, cfg)
     g.build(data)
     keys, counts = om.export(canonical=True)
-    rng = np.random.default_rng(k)
+    rng = np.random.default_rng(seed)
     pick = rng.permutation(keys.shape[0])[: keys.shape[0] // 3]
     victims = keys[pick]
-    absent = orc.extract(s, bytes(K.synth_fastq(seed=91, genome_len=50000, n_reads=15)), orc.FASTQ)["kmers"]
     q = np.concatenate([victims[::2], orc.revcomp(s, victims[1::2]), absent, victims[:25]])
     gone = {tuple(r) for r in orc.canonical(s, q).tolist()} & {tuple(r) for r in keys.tolist()}
     assert g.erase(q) == len(gone)
@@ -120,7 +135,6 @@ def test_erase_nodes(ctx, k, alpha):
     assert g.find(victims)[0].shape[0] == 0
     assert g.erase(victims) == 0                                    # nothing left to erase
     # the map goes on from what stayed: a second batch meets the surviving nodes' counts
-    data2 = _with_n(bytes(K.synth_fastq(seed=3 * k, genome_len=5000, n_reads=600, first_read=2500)), k + 1)
     k2, e2 = orc.dbg_parse(s, data2)
     om2 = orc.DbgMap(s)
     survivors = np.array([tuple(r) not in gone for r in orc.canonical(s, ok).tolist()])

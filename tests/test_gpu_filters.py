@@ -8,6 +8,7 @@ import numpy as np
 import pytest
 
 from tests import oracle as orc
+from tests.shape_cases import ALPHA
 
 pytestmark = pytest.mark.gpu
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
@@ -45,7 +46,7 @@ def _fastq_with_n(seed, n_reads, n_marks):
 
 def _check_extract(ctx, data, fmt, k, alpha, flt, with_ids=True):
     import kmerind_amd as K
-    s = orc.kspec(k, orc.DNA if alpha == "DNA" else orc.DNA5)
+    s = orc.kspec(k, ALPHA[alpha])
     cfg = K.make_config(k, alpha, strand="single", seq_format=fmt, seq_filter=flt,
                         index_kind="position" if with_ids else "count")
     ex = orc.extract(s, data, orc.FASTQ if fmt == "fastq" else orc.FASTA, want_ids=with_ids, seq_filter=FILTERS[flt])

@@ -163,44 +163,47 @@ def test_many_distinct_keys_multi_pass_buckets(ctx):
 
 
 def test_route_matches_key_to_rank(ctx):
-    import ctypes as C
     import kmerind_amd as K
-    from kmerind_amd import _lib as L
     for k, alpha, strand, dh in ((31, "DNA", "canonical", "murmur"), (63, "DNA5", "bimolecule", "farm"), (21, "DNA", "single", "murmur")):
         cfg = K.make_config(k, alpha, strand=strand, dist_hash=dh)
         s = orc.kspec(k, ALPHA[alpha])
         ex = orc.extract(s, K.synth_fastq(seed=3, genome_len=50000, n_reads=800), orc.FASTQ)["kmers"]
-        n, nw = ex.shape
-        for p in (1, 2, 5, 8):
-            din, dout = ctx.alloc(ex.nbytes), ctx.alloc(ex.nbytes)
-            ctx.to_device(din, ex)
-            counts = np.zeros(p, dtype=np.uint64)
-            ctx.check(L.lib.kmi_route_dev(ctx.h, C.byref(cfg), C.c_void_p(din), n, p, C.c_void_p(dout),
-                                          counts.ctypes.data_as(C.c_void_p)))
-            out = np.zeros_like(ex)
-            ctx.to_host(out, dout)
-            ctx.free(din); ctx.free(dout)
-            # reference: transform_input, then rank = DistHash(DistTrans(key)) % p
-            tk = ex if strand == "single" else orc.canonical(s, ex)
-            ranks = orc.key_to_rank(s, orc.MURMUR if dh == "murmur" else orc.FARM, STRAND[strand], tk, p)
-            assert counts.tolist() == np.bincount(ranks, minlength=p).tolist()
-            off = 0
-            for r in range(p):
-                seg = out[off:off + int(counts[r])]
-                exp = tk[ranks == r]
-                a = seg[np.lexsort([seg[:, w] for w in range(nw)])]
-                b = exp[np.lexsort([exp[:, w] for w in range(nw)])]
-                assert (a == b).all()
-                off += int(counts[r])
+        check_route(ctx, s, cfg, strand, orc.MURMUR if dh == "murmur" else orc.FARM, ex, (1, 2, 5, 8))
+
+
+def check_route(ctx, s, cfg, strand, dist_hash, ex, ps):
+    """kmi_route_dev of the k-mers `ex` for every rank count of `ps`: shared with test_gpu_shape_matrix.py"""
+    import ctypes as C
+    from kmerind_amd import _lib as L
+    n, nw = ex.shape
+    for p in ps:
+        din, dout = ctx.alloc(ex.nbytes), ctx.alloc(ex.nbytes)
+        ctx.to_device(din, ex)
+        counts = np.zeros(p, dtype=np.uint64)
+        ctx.check(L.lib.kmi_route_dev(ctx.h, C.byref(cfg), C.c_void_p(din), n, p, C.c_void_p(dout),
+                                      counts.ctypes.data_as(C.c_void_p)))
+        out = np.zeros_like(ex)
+        ctx.to_host(out, dout)
+        ctx.free(din); ctx.free(dout)
+        # reference: transform_input, then rank = DistHash(DistTrans(key)) % p
+        tk = ex if strand == "single" else orc.canonical(s, ex)
+        ranks = orc.key_to_rank(s, dist_hash, STRAND[strand], tk, p)
+        assert counts.tolist() == np.bincount(ranks, minlength=p).tolist()
+        off = 0
+        for r in range(p):
+            seg = out[off:off + int(counts[r])]
+            exp = tk[ranks == r]
+            a = seg[np.lexsort([seg[:, w] for w in range(nw)])]
+            b = exp[np.lexsort([exp[:, w] for w in range(nw)])]
+            assert (a == b).all()
+            off += int(counts[r])
 
 
 def test_extract_route_fused_matches_extract_then_key_to_rank(ctx):
     """kmi_extract_route_dev = read_file + the bucketing half of imxx::distribute: per destination rank the same
     multiset of transformed keys as oracle extract -> transform -> KeyToRank; then the whole multi-rank build replayed
     on one device (every rank's reads routed, every destination's index built) equals the oracle's single map."""
-    import ctypes as C
     import kmerind_amd as K
-    from kmerind_amd import _lib as L
     for k, alpha, strand, dh, p in ((31, "DNA", "canonical", "murmur", 8), (21, "DNA", "single", "farm", 3),
                                     (63, "DNA5", "canonical", "murmur", 2), (31, "DNA", "bimolecule", "identity", 5)):
         cfg = K.make_config(k, alpha, strand=strand, dist_hash=dh)
@@ -210,29 +213,10 @@ def test_extract_route_fused_matches_extract_then_key_to_rank(ctx):
         all_kmers = []
         for r in range(p):                                    # rank r parses its own reads
             data = np.asarray(K.synth_fastq(seed=7, genome_len=60000, n_reads=500, first_read=r * 500))
-            ex = orc.extract(s, data.tobytes(), orc.FASTQ)["kmers"]
+            ex, segs = check_extract_route(ctx, s, cfg, strand, hashes[dh], data, p, 500)
             all_kmers.append(ex)
-            n, nw = ex.shape
-            dbytes, dout = ctx.alloc(data.nbytes), ctx.alloc(ex.nbytes + 64)
-            ctx.to_device(dbytes, data)
-            counts = np.zeros(p, dtype=np.uint64)
-            nt, ns = C.c_uint64(), C.c_uint64()
-            ctx.check(L.lib.kmi_extract_route_dev(ctx.h, C.byref(cfg), C.c_void_p(dbytes), data.nbytes, p, C.c_void_p(dout), n,
-                                                  C.byref(nt), C.byref(ns), counts.ctypes.data_as(C.c_void_p)))
-            assert nt.value == n and ns.value == 500
-            out = np.zeros_like(ex)
-            ctx.to_host(out, dout)
-            ctx.free(dbytes); ctx.free(dout)
-            tk = ex if strand == "single" else orc.canonical(s, ex)
-            ranks = orc.key_to_rank(s, hashes[dh], STRAND[strand], tk, p)
-            assert counts.tolist() == np.bincount(ranks, minlength=p).tolist()
-            off = 0
             for d in range(p):
-                seg = out[off:off + int(counts[d])]
-                exp = tk[ranks == d]
-                assert (seg[np.lexsort([seg[:, w] for w in range(nw)])] == exp[np.lexsort([exp[:, w] for w in range(nw)])]).all()
-                per_dest[d].append(seg)
-                off += int(counts[d])
+                per_dest[d].append(segs[d])
         m = orc.CountMap(s, STRAND[strand])
         m.insert(np.concatenate(all_kmers))
         got_k, got_c = [], []
@@ -249,6 +233,36 @@ def test_extract_route_fused_matches_extract_then_key_to_rank(ctx):
         assert (gk[go] == ek[eo]).all() and (gc[go] == ec[eo]).all()
 
 
+def check_extract_route(ctx, s, cfg, strand, dist_hash, data, p, n_seqs):
+    """kmi_extract_route_dev of one rank's FASTQ bytes (numpy uint8) for p ranks -> (the oracle's k-mers, the segment of every
+    destination): shared with test_gpu_shape_matrix.py"""
+    import ctypes as C
+    from kmerind_amd import _lib as L
+    ex = orc.extract(s, data.tobytes(), orc.FASTQ)["kmers"]
+    n, nw = ex.shape
+    dbytes, dout = ctx.alloc(data.nbytes), ctx.alloc(ex.nbytes + 64)
+    ctx.to_device(dbytes, data)
+    counts = np.zeros(p, dtype=np.uint64)
+    nt, ns = C.c_uint64(), C.c_uint64()
+    ctx.check(L.lib.kmi_extract_route_dev(ctx.h, C.byref(cfg), C.c_void_p(dbytes), data.nbytes, p, C.c_void_p(dout), n,
+                                          C.byref(nt), C.byref(ns), counts.ctypes.data_as(C.c_void_p)))
+    assert nt.value == n and ns.value == n_seqs
+    out = np.zeros_like(ex)
+    ctx.to_host(out, dout)
+    ctx.free(dbytes); ctx.free(dout)
+    tk = ex if strand == "single" else orc.canonical(s, ex)
+    ranks = orc.key_to_rank(s, dist_hash, STRAND[strand], tk, p)
+    assert counts.tolist() == np.bincount(ranks, minlength=p).tolist()
+    off, segs = 0, []
+    for d in range(p):
+        seg = out[off:off + int(counts[d])]
+        exp = tk[ranks == d]
+        assert (seg[np.lexsort([seg[:, w] for w in range(nw)])] == exp[np.lexsort([exp[:, w] for w in range(nw)])]).all()
+        segs.append(seg)
+        off += int(counts[d])
+    return ex, segs
+
+
 def test_combine_first_split_and_merge_replayed_on_one_device(ctx):
     """The N > 1 count build, combine-first (kmi_index_split_by_rank_dev / kmi_index_merge_parts_dev): every rank's local
     index split by KeyToRank -- message d holds exactly the entries whose key maps to rank d, ordered by placement
@@ -256,63 +270,86 @@ def test_combine_first_split_and_merge_replayed_on_one_device(ctx):
     on one device, equal the oracle's single map restricted to the keys of that rank. A second round merges into the
     non-empty index (the index grows incrementally, like repeated Index::insert)."""
     import kmerind_amd as K
-    nb = K.core.num_buckets()
     for k, alpha, strand, dh, p in ((31, "DNA", "canonical", "murmur", 8), (21, "DNA", "single", "farm", 3),
                                     (63, "DNA5", "canonical", "murmur", 2), (31, "DNA", "bimolecule", "identity", 5),
                                     (15, "DNA", "canonical", "murmur", 1)):
         cfg = K.make_config(k, alpha, strand=strand, dist_hash=dh)
         s = orc.kspec(k, ALPHA[alpha])
         hashes = {"murmur": orc.MURMUR, "farm": orc.FARM, "identity": orc.IDENTITY}
-        dest = [K.CountIndex(ctx, cfg) for _ in range(p)]
-        all_kmers = []
-        for rnd in range(2):
-            msgs = [[None] * p for _ in range(p)]                 # msgs[d][src] = (keys, counts, bucket counts)
-            for r in range(p):                                    # rank r reduces its own reads, then splits
-                data = np.asarray(K.synth_fastq(seed=11, genome_len=3000, n_reads=300, first_read=(rnd * p + r) * 300))
-                all_kmers.append(orc.extract(s, data.tobytes(), orc.FASTQ)["kmers"])
-                loc = K.CountIndex(ctx, cfg)
-                loc.build(data)
-                n, nw = loc.local_size(), loc.n_words
-                lk, lc = loc.to_vector()
-                dk, dc, db = ctx.alloc(n * nw * 8 + 64), ctx.alloc(n * 4 + 64), ctx.alloc(p * nb * 4)
-                sc = loc.split_by_rank_device(p, dk, dc, n, db)
-                ok, oc, ob = np.zeros((n, nw), np.uint64), np.zeros(n, np.uint32), np.zeros((p, nb), np.uint32)
-                ctx.to_host(ok, dk); ctx.to_host(oc, dc); ctx.to_host(ob, db)
-                ctx.free(dk); ctx.free(dc); ctx.free(db)
-                assert loc.local_size() == n                      # the split leaves the index as it was
-                loc.close()
-                ranks = orc.key_to_rank(s, hashes[dh], STRAND[strand], lk, p)
-                assert sc.tolist() == np.bincount(ranks, minlength=p).tolist() == ob.sum(axis=1).tolist()
-                off = 0
-                for d in range(p):
-                    seg_k, seg_c = ok[off:off + int(sc[d])], oc[off:off + int(sc[d])]
-                    a, b = orc.sorted_pairs(seg_k, seg_c), orc.sorted_pairs(lk[ranks == d], lc[ranks == d])
-                    assert (a[0] == b[0]).all() and (a[1] == b[1]).all()
-                    msgs[d][r] = (seg_k, seg_c, ob[d])
-                    off += int(sc[d])
-            for d in range(p):                                    # destination d merges the p parts it received
-                mk = np.concatenate([m[0] for m in msgs[d]]); mc = np.concatenate([m[1] for m in msgs[d]])
-                mb = np.stack([m[2] for m in msgs[d]])
-                dk, dc, db = ctx.alloc(mk.nbytes + 64), ctx.alloc(mc.nbytes + 64), ctx.alloc(mb.nbytes)
-                if mk.size:
-                    ctx.to_device(dk, mk); ctx.to_device(dc, mc)
-                ctx.to_device(db, np.ascontiguousarray(mb))
-                dest[d].merge_parts_device(p, dk, dc, db)
-                ctx.free(dk); ctx.free(dc); ctx.free(db)
-        m = orc.CountMap(s, STRAND[strand])
-        m.insert(np.concatenate(all_kmers))
-        ek, ec = m.export()
-        eranks = orc.key_to_rank(s, hashes[dh], STRAND[strand], ek, p)
-        for d in range(p):
-            gk, gc = dest[d].to_vector()
-            a, b = orc.sorted_pairs(gk, gc), orc.sorted_pairs(ek[eranks == d], ec[eranks == d])
-            assert a[0].shape == b[0].shape and (a[0] == b[0]).all() and (a[1] == b[1]).all()
-            dest[d].close()
+        check_split_and_merge_replay(ctx, s, cfg, strand, hashes[dh], p, lambda rnd, r: np.asarray(
+            K.synth_fastq(seed=11, genome_len=3000, n_reads=300, first_read=(rnd * p + r) * 300)))
 
 
-def _keys_in_one_placement_bucket(n, bucket, hi_words=(1, 77, 1 << 20)):
-    """white-box helper: one-word keys whose placement hash (kmi_device.h place_hash: three 32-bit multiply / xorshift
-    rounds, a bijection of the low word for a fixed high word) falls into fine bucket `bucket` -- found by inverting it."""
+def check_split_and_merge_replay(ctx, s, cfg, strand, dist_hash, p, reads_of):
+    """two rounds of p ranks: rank r builds reads_of(round, r) (FASTQ bytes as numpy uint8), splits by rank, every destination
+    merges its p parts: shared with test_gpu_shape_matrix.py"""
+    import kmerind_amd as K
+    nb = K.core.num_buckets()
+    dest = [K.CountIndex(ctx, cfg) for _ in range(p)]
+    all_kmers = []
+    for rnd in range(2):
+        msgs = [[None] * p for _ in range(p)]                 # msgs[d][src] = (keys, counts, bucket counts)
+        for r in range(p):                                    # rank r reduces its own reads, then splits
+            data = reads_of(rnd, r)
+            all_kmers.append(orc.extract(s, data.tobytes(), orc.FASTQ)["kmers"])
+            loc = K.CountIndex(ctx, cfg)
+            loc.build(data)
+            n, nw = loc.local_size(), loc.n_words
+            lk, lc = loc.to_vector()
+            dk, dc, db = ctx.alloc(n * nw * 8 + 64), ctx.alloc(n * 4 + 64), ctx.alloc(p * nb * 4)
+            sc = loc.split_by_rank_device(p, dk, dc, n, db)
+            ok, oc, ob = np.zeros((n, nw), np.uint64), np.zeros(n, np.uint32), np.zeros((p, nb), np.uint32)
+            ctx.to_host(ok, dk); ctx.to_host(oc, dc); ctx.to_host(ob, db)
+            ctx.free(dk); ctx.free(dc); ctx.free(db)
+            assert loc.local_size() == n                      # the split leaves the index as it was
+            loc.close()
+            ranks = orc.key_to_rank(s, dist_hash, STRAND[strand], lk, p)
+            assert sc.tolist() == np.bincount(ranks, minlength=p).tolist() == ob.sum(axis=1).tolist()
+            off = 0
+            for d in range(p):
+                seg_k, seg_c = ok[off:off + int(sc[d])], oc[off:off + int(sc[d])]
+                a, b = orc.sorted_pairs(seg_k, seg_c), orc.sorted_pairs(lk[ranks == d], lc[ranks == d])
+                assert (a[0] == b[0]).all() and (a[1] == b[1]).all()
+                msgs[d][r] = (seg_k, seg_c, ob[d])
+                off += int(sc[d])
+        for d in range(p):                                    # destination d merges the p parts it received
+            mk = np.concatenate([m[0] for m in msgs[d]]); mc = np.concatenate([m[1] for m in msgs[d]])
+            mb = np.stack([m[2] for m in msgs[d]])
+            dk, dc, db = ctx.alloc(mk.nbytes + 64), ctx.alloc(mc.nbytes + 64), ctx.alloc(mb.nbytes)
+            if mk.size:
+                ctx.to_device(dk, mk); ctx.to_device(dc, mc)
+            ctx.to_device(db, np.ascontiguousarray(mb))
+            dest[d].merge_parts_device(p, dk, dc, db)
+            ctx.free(dk); ctx.free(dc); ctx.free(db)
+    m = orc.CountMap(s, STRAND[strand])
+    m.insert(np.concatenate(all_kmers))
+    ek, ec = m.export()
+    eranks = orc.key_to_rank(s, dist_hash, STRAND[strand], ek, p)
+    for d in range(p):
+        gk, gc = dest[d].to_vector()
+        a, b = orc.sorted_pairs(gk, gc), orc.sorted_pairs(ek[eranks == d], ec[eranks == d])
+        assert a[0].shape == b[0].shape and (a[0] == b[0]).all() and (a[1] == b[1]).all()
+        dest[d].close()
+
+
+def place_hash_np(keys):
+    """kmi_device.h place_hash restated in numpy for (n, n_words) uint64 keys -> uint32 hashes as uint64"""
+    M = np.uint64(0xffffffff)
+    keys = np.ascontiguousarray(keys, dtype=np.uint64).reshape(len(keys), -1)
+    h = np.full(keys.shape[0], 0x9E3779B9, dtype=np.uint64)
+    for w in range(keys.shape[1]):
+        h = ((h ^ (keys[:, w] & M)) * np.uint64(0x85EBCA6B)) & M
+        h ^= h >> np.uint64(15)
+        h = ((h ^ (keys[:, w] >> np.uint64(32))) * np.uint64(0xC2B2AE35)) & M
+        h ^= h >> np.uint64(13)
+    h = (h * np.uint64(0x27D4EB2F)) & M
+    return h ^ (h >> np.uint64(16))
+
+
+def _keys_in_one_placement_bucket(n, bucket, hi_words=(1, 77, 1 << 20), later_words=()):
+    """white-box helper: keys whose placement hash (kmi_device.h place_hash: per word two 32-bit multiply / xorshift rounds and
+    a last one, a bijection of word 0's low half when everything else is fixed) falls into fine bucket `bucket` -- found by
+    inverting it. One-word keys as a flat array; with later_words (the fixed words 1.. of every key) an (n, n_words) array."""
     M = np.uint64(0xffffffff)
 
     def inv_mul(c):
@@ -330,12 +367,23 @@ def _keys_in_one_placement_bucket(n, bucket, hi_words=(1, 77, 1 << 20)):
         h = (np.uint64(bucket) << np.uint64(17)) | np.arange(per, dtype=np.uint64)      # final hash values in the bucket
         h = unshift(h, 16)
         h = (h * inv_mul(0x27D4EB2F)) & M
-        h = unshift(h, 13)
-        h = ((h * inv_mul(0xC2B2AE35)) & M) ^ np.uint64(hi)
-        h = unshift(h, 15)
-        lo = ((h * inv_mul(0x85EBCA6B)) & M) ^ np.uint64(0x9E3779B9)
+        for word in tuple(later_words)[::-1] + (None,):
+            w_hi, w_lo = (hi, None) if word is None else (int(word) >> 32, int(word) & 0xffffffff)
+            h = unshift(h, 13)
+            h = ((h * inv_mul(0xC2B2AE35)) & M) ^ np.uint64(w_hi)
+            h = unshift(h, 15)
+            h = (h * inv_mul(0x85EBCA6B)) & M
+            if w_lo is not None:
+                h ^= np.uint64(w_lo)
+        lo = h ^ np.uint64(0x9E3779B9)
         out.append((np.uint64(hi) << np.uint64(32)) | lo)
-    return np.concatenate(out)[:n]
+    word0 = np.concatenate(out)[:n]
+    if not later_words:
+        return word0
+    keys = np.empty((n, 1 + len(later_words)), dtype=np.uint64)
+    keys[:, 0] = word0
+    keys[:, 1:] = np.array(later_words, dtype=np.uint64)
+    return keys
 
 
 @pytest.mark.parametrize("n_hot", [30_000, 250_000])
@@ -868,17 +916,24 @@ def test_update_with_device_updaters(k, alpha, strand):
     import kmerind_amd as K
     ctx = K.Context(0)
     s = orc.kspec(k, ALPHA[alpha])
-    st = STRAND[strand]
     data = bytes(K.synth_fastq(seed=k, genome_len=5000, n_reads=1500))
+    absent = orc.extract(s, bytes(K.synth_fastq(seed=91, genome_len=40000, n_reads=20)), orc.FASTQ)["kmers"]
+    check_update_with_device_updaters(ctx, s, K.make_config(k, alpha, strand=strand), strand, data, absent, seed=k)
+    ctx.close()
+
+
+def check_update_with_device_updaters(ctx, s, cfg, strand, data, absent, seed):
+    """add, max, min, assign, add in sequence on an index built from `data`: shared with test_gpu_shape_matrix.py"""
+    import kmerind_amd as K
+    st = STRAND[strand]
     kmers = orc.extract(s, data, orc.FASTQ)["kmers"]
-    idx = K.CountIndex(ctx, K.make_config(k, alpha, strand=strand))
+    idx = K.CountIndex(ctx, cfg)
     idx.build(data)
     om = orc.CountMap(s, st)
     om.insert(kmers)
     keys, cnt = om.export()
     ref = {tuple(a): int(b) for a, b in zip(keys.tolist(), cnt.tolist())}
-    rng = np.random.default_rng(k)
-    absent = orc.extract(s, bytes(K.synth_fastq(seed=91, genome_len=40000, n_reads=20)), orc.FASTQ)["kmers"]
+    rng = np.random.default_rng(seed)
 
     def canon(q):
         return q if strand == "single" else orc.canonical(s, q)
@@ -897,7 +952,6 @@ def test_update_with_device_updaters(k, alpha, strand):
         gk, gc = idx.to_vector()
         assert gk.shape[0] == len(ref) and all(ref[tuple(a)] == int(b) for a, b in zip(gk.tolist(), gc.tolist()))
     idx.close()
-    ctx.close()
 
 
 @pytest.mark.parametrize("k,strand,kind", [(31, "canonical", "plain"), (21, "single", "plain"), (31, "canonical", "malformed"), (31, "canonical", "fasta"),

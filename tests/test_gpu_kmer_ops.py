@@ -7,13 +7,14 @@ import numpy as np
 import pytest
 
 from tests import oracle as orc
+from tests.shape_cases import NEW
 
 pytestmark = pytest.mark.gpu
 
 GOLD = os.path.join(os.path.dirname(__file__), "golden")
 SHAPES = [(31, "DNA"), (21, "DNA"), (32, "DNA"), (1, "DNA"), (63, "DNA"), (96, "DNA"),
-          (21, "DNA5"), (35, "DNA5"), (63, "DNA5"), (13, "DNA5")]
-ALPHA = {"DNA": orc.DNA, "DNA5": orc.DNA5}
+          (21, "DNA5"), (35, "DNA5"), (63, "DNA5"), (13, "DNA5"), (16, "DNA16")] + NEW
+ALPHA = {"DNA": orc.DNA, "DNA5": orc.DNA5, "DNA16": orc.DNA16}
 
 
 @pytest.fixture(scope="module")

@@ -35,6 +35,14 @@ def test_position_index_build_insert_query(ctx, k, alpha, strand):
     s = orc.kspec(k, ALPHA[alpha])
     cfg = K.make_config(k, alpha, strand=strand, index_kind="position")
     data = bytes(K.synth_fastq(seed=k, genome_len=3000, n_reads=1200))
+    data2 = bytes(K.synth_fastq(seed=k, genome_len=3000, n_reads=500, first_read=5000))
+    absent = orc.extract(s, bytes(K.synth_fastq(seed=99, genome_len=50000, n_reads=30)), orc.FASTQ)["kmers"]
+    check_build_insert_query(ctx, s, cfg, strand, data, data2, absent, seed=k)
+
+
+def check_build_insert_query(ctx, s, cfg, strand, data, data2, absent, seed):
+    """build from `data`, insert(tuples) of `data2` at another file offset, count / find / erase: shared with test_gpu_shape_matrix.py"""
+    import kmerind_amd as K
     ex = orc.extract(s, data, orc.FASTQ, want_ids=True)
     om = orc.MultiMap(s, STRAND[strand])
     om.insert(ex["kmers"], ex["ids"])
@@ -43,15 +51,13 @@ def test_position_index_build_insert_query(ctx, k, alpha, strand):
     assert idx.local_size() == ex["kmers"].shape[0]
     _same(idx, om)
     # a second batch through insert(tuples) at another file offset
-    data2 = bytes(K.synth_fastq(seed=k, genome_len=3000, n_reads=500, first_read=5000))
     ex2 = orc.extract(s, data2, orc.FASTQ, file_offset=1 << 33, want_ids=True)
     om.insert(ex2["kmers"], ex2["ids"])
     idx.insert(ex2["kmers"], ex2["ids"])
     _same(idx, om)
     # queries: present (with repeats), absent
-    rng = np.random.default_rng(k)
+    rng = np.random.default_rng(seed)
     present = ex["kmers"][rng.integers(0, ex["kmers"].shape[0], size=3000)]
-    absent = orc.extract(s, bytes(K.synth_fastq(seed=99, genome_len=50000, n_reads=30)), orc.FASTQ)["kmers"]
     q = np.concatenate([present, absent, present[:50]])
     gk, gc = idx.count(q)
     ok, oc = om.count(q)
@@ -103,13 +109,18 @@ def test_position_index_api_guards(ctx):
 
 def test_route_tuples_matches_key_to_rank(ctx):
     """imxx::distribute on (k-mer, id) records: grouped by KeyToRank, payload carried along"""
-    import ctypes as C
     import kmerind_amd as K
-    from kmerind_amd import _lib as L
     k, p = 31, 5
     s = orc.kspec(k, orc.DNA)
     cfg = K.make_config(k, "DNA", strand="canonical", index_kind="position")
-    ex = orc.extract(s, bytes(K.synth_fastq(seed=2, genome_len=30000, n_reads=900)), orc.FASTQ, want_ids=True)
+    check_route_tuples(ctx, s, cfg, bytes(K.synth_fastq(seed=2, genome_len=30000, n_reads=900)), p)
+
+
+def check_route_tuples(ctx, s, cfg, data, p):
+    """kmi_route_tuples_dev of the (k-mer, id) tuples of a FASTQ buffer, canonical strand model: shared with test_gpu_shape_matrix.py"""
+    import ctypes as C
+    from kmerind_amd import _lib as L
+    ex = orc.extract(s, data, orc.FASTQ, want_ids=True)
     rec = np.ascontiguousarray(np.concatenate([ex["kmers"], ex["ids"][:, None]], axis=1))
     n = rec.shape[0]
     din, dout = ctx.alloc(rec.nbytes), ctx.alloc(rec.nbytes)
@@ -135,13 +146,18 @@ def test_route_tuples_matches_key_to_rank(ctx):
 def test_extract_route_records_matches_key_to_rank(ctx, kind):
     """kmi_extract_route_records_dev = kmi_extract_records_dev + kmi_route_tuples_dev: the (k-mer, id[, quality]) tuples of a
     FASTQ buffer at a file offset, canonical k-mers grouped by KeyToRank with their values carried along"""
-    import ctypes as C
     import kmerind_amd as K
-    from kmerind_amd import _lib as L
     k, p, off0 = 31, 3, 7_000_000
     s = orc.kspec(k, orc.DNA)
     cfg = K.make_config(k, "DNA", strand="canonical", index_kind=kind)
     data = bytes(K.synth_fastq(seed=12, genome_len=30000, n_reads=700))
+    check_extract_route_records(ctx, s, cfg, kind, data, p, off0, 700)
+
+
+def check_extract_route_records(ctx, s, cfg, kind, data, p, off0, n_seqs):
+    """shared with test_gpu_shape_matrix.py (canonical strand model)"""
+    import ctypes as C
+    from kmerind_amd import _lib as L
     ex = orc.extract(s, data, orc.FASTQ, want_ids=True, want_quals=(kind == "posqual"), file_offset=off0)
     cols = [ex["kmers"], ex["ids"][:, None]]
     if kind == "posqual":
@@ -154,7 +170,7 @@ def test_extract_route_records_matches_key_to_rank(ctx, kind):
     nt, ns = C.c_uint64(0), C.c_uint64(0)
     ctx.check(L.lib.kmi_extract_route_records_dev(ctx.h, C.byref(cfg), C.c_void_p(din), raw.nbytes, off0, p, C.c_void_p(dout), n,
                                                   C.byref(nt), C.byref(ns), counts.ctypes.data_as(C.c_void_p)))
-    assert nt.value == n and ns.value == 700
+    assert nt.value == n and ns.value == n_seqs
     out = np.zeros((n, rw), dtype=np.uint64)
     ctx.to_host(out, dout)
     with pytest.raises(L.KmiError):      # capacity

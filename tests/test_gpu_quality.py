@@ -44,12 +44,17 @@ def test_kmer_quality_bit_exact(ctx, k):
     inputs.append(_fastq_with_quals(rng, 200, lo=33, hi=129))          # the whole LUT incl. Q94/Q95
     inputs.append(bytes(K.synth_fastq(seed=6, genome_len=50_000, n_reads=1500)))
     for data in inputs:
-        ex = orc.extract(s, data, orc.FASTQ, want_ids=True, want_quals=True)
-        kmers, ids, quals, nseq = ctx.read_file(cfg, data, with_ids=True, with_quals=True)
-        assert kmers.shape == ex["kmers"].shape and (kmers == ex["kmers"]).all() and (ids == ex["ids"]).all()
-        assert quals.dtype == np.float32
-        assert (quals.view(np.uint32) == ex["quals"].view(np.uint32)).all()
-        assert (quals >= 0).all() and (quals <= 1.0 + 1e-5).all()   # the running float sum may drift a hair above 0
+        check_quality_bit_exact(ctx, s, cfg, data)
+
+
+def check_quality_bit_exact(ctx, s, cfg, data):
+    """(k-mer, id, quality) tuples of a FASTQ buffer, the float bit for bit: shared with test_gpu_shape_matrix.py"""
+    ex = orc.extract(s, data, orc.FASTQ, want_ids=True, want_quals=True)
+    kmers, ids, quals, nseq = ctx.read_file(cfg, data, with_ids=True, with_quals=True)
+    assert kmers.shape == ex["kmers"].shape and (kmers == ex["kmers"]).all() and (ids == ex["ids"]).all()
+    assert quals.dtype == np.float32
+    assert (quals.view(np.uint32) == ex["quals"].view(np.uint32)).all()
+    assert (quals >= 0).all() and (quals <= 1.0 + 1e-5).all()   # the running float sum may drift a hair above 0
 
 
 def test_position_quality_index(ctx):
@@ -58,6 +63,12 @@ def test_position_quality_index(ctx):
     s = orc.kspec(k, orc.DNA)
     cfg = K.make_config(k, "DNA", strand="canonical", index_kind="posqual")
     data = bytes(K.synth_fastq(seed=12, genome_len=5000, n_reads=800))
+    check_position_quality_index(ctx, s, cfg, data)
+
+
+def check_position_quality_index(ctx, s, cfg, data):
+    """canonical (k-mer, id, quality bits) rows of a build, find and count: shared with test_gpu_shape_matrix.py"""
+    import kmerind_amd as K
     ex = orc.extract(s, data, orc.FASTQ, want_ids=True, want_quals=True)
     vals = np.stack([ex["ids"], ex["quals"].view(np.uint32).astype(np.uint64)], axis=1)
     mm = orc.MultiMap(s, orc.CANONICAL, vw=2)

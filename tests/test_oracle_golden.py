@@ -75,12 +75,20 @@ def test_reverse_known_answers():
 
 
 def test_revcomp_is_bitwise_rule():
-    """DNA: rc == ~group_reverse ; DNA5: rc == full bit reversal (kmer.hpp:1723-1742,1807-1847)"""
+    """DNA: rc == ~group_reverse ; DNA5: rc == full bit reversal (kmer.hpp:1723-1742,1807-1847); DNA16: the characters in
+    reverse order, every nibble bit-reversed (the complement of the FROM_ASCII table's IUPAC codes)"""
+    from tests.shape_cases import ALPHA, IUPAC_COMPLEMENT, NEW
     rng = np.random.default_rng(7)
-    for k, alpha in ((31, orc.DNA), (21, orc.DNA), (63, orc.DNA), (63, orc.DNA5), (21, orc.DNA5), (32, orc.DNA)):
+    letters = {orc.DNA: b"ACGT", orc.DNA5: b"ACGTN", orc.DNA16: "".join(IUPAC_COMPLEMENT).encode()}
+    from_ascii = _load("alphabet_tables.json")["DNA16_T"]
+    for a, b in IUPAC_COMPLEMENT.items():      # the text-level complement is the nibble-wise bit reversal of the code
+        assert from_ascii[ord(b)] == int(format(from_ascii[ord(a)], "04b")[::-1], 2), (a, b)
+        assert from_ascii[ord(a.lower())] == from_ascii[ord(a)]
+    assert sorted(from_ascii[c] for c in letters[orc.DNA16]) == list(range(1, 16))
+    for k, alpha in [(31, orc.DNA), (21, orc.DNA), (63, orc.DNA), (63, orc.DNA5), (21, orc.DNA5), (32, orc.DNA)] + [(k, ALPHA[a]) for k, a in NEW]:
         s = orc.kspec(k, alpha)
         for _ in range(50):
-            text = bytes(rng.choice(list(b"ACGT" if alpha == orc.DNA else b"ACGTN"), size=k).tolist())
+            text = bytes(rng.choice(list(letters[alpha]), size=k).tolist())
             km = orc.kmers_from_string(s, text)[0]
             rc = orc.revcomp(s, km)[0]
             big = sum(int(km[w]) << (64 * w) for w in range(s.n_words))
@@ -88,12 +96,17 @@ def test_revcomp_is_bitwise_rule():
                 rev = 0
                 for i in range(k):
                     rev |= (3 - ((big >> (2 * i)) & 3)) << (2 * (k - 1 - i))
-            else:
+            elif alpha == orc.DNA5:
                 rev = int(format(big, "0%db" % s.n_bits)[::-1], 2)
+            else:
+                rev = 0
+                for i in range(k):
+                    rev |= int(format((big >> (4 * i)) & 15, "04b")[::-1], 2) << (4 * (k - 1 - i))
+                assert rev == int(format(big, "0%db" % s.n_bits)[::-1], 2)      # (which is the full bit reversal again)
             got = sum(int(rc[w]) << (64 * w) for w in range(s.n_words))
             assert got == rev
             # rc of the text-level reverse complement
-            comp = bytes.maketrans(b"ACGTN", b"TGCAN")
+            comp = bytes.maketrans("".join(IUPAC_COMPLEMENT).encode(), "".join(IUPAC_COMPLEMENT.values()).encode())
             assert orc.kmers_from_string(s, text.translate(comp)[::-1])[0].tolist() == rc.tolist()
 
 
@@ -345,6 +358,17 @@ def test_identity_and_std_hashers_follow_the_cited_formulas():
     h = ((w[0] << 1) ^ (w[1] << 1) ^ (w[2] << 1)) & M
     assert int(orc.kmer_hash(s3, orc.STD, False, km3)[0]) == h
     assert int(orc.kmer_hash(s3, orc.STD, True, km3)[0]) == h >> (64 - 32)
+    s4 = orc.kspec(128, orc.DNA)   # 256 bits in 4 words, no pad bits: the prefix is the top of the last word
+    w = [0x0123456789ABCDEF, 0xFEDCBA9876543210, 0x0F1E2D3C4B5A6978, 0x8796A5B4C3D2E1F0]
+    km4 = np.array([w], dtype=np.uint64)
+    assert int(orc.kmer_hash(s4, orc.IDENTITY, False, km4)[0]) == w[0]
+    assert int(orc.kmer_hash(s4, orc.IDENTITY, True, km4)[0]) == w[3] >> (64 - 24)
+    h = ((w[0] << 1) ^ (w[1] << 1) ^ (w[2] << 1) ^ (w[3] << 1)) & M
+    assert int(orc.kmer_hash(s4, orc.STD, False, km4)[0]) == h
+    assert int(orc.kmer_hash(s4, orc.STD, True, km4)[0]) == h >> (64 - 32)
+    for p, bits in ((2, 1), (3, 2), (200, 8)):
+        assert int(orc.key_to_rank(s4, orc.IDENTITY, orc.SINGLE, km4, p)[0]) == (w[3] >> (64 - bits)) % p
+        assert int(orc.key_to_rank(s4, orc.STD, orc.SINGLE, km4, p)[0]) == (h >> (64 - bits)) % p
 
 
 def test_std_hasher_against_the_standard_library_the_reference_calls():
@@ -360,7 +384,8 @@ def test_std_hasher_against_the_standard_library_the_reference_calls():
     probe.argtypes, probe.restype = [C.c_size_t], C.c_size_t
     M = (1 << 64) - 1
     rng = np.random.default_rng(4)
-    for k, alpha in ((31, orc.DNA), (21, orc.DNA), (33, orc.DNA), (63, orc.DNA5), (96, orc.DNA), (16, orc.DNA16)):
+    from tests.shape_cases import ALPHA, NEW
+    for k, alpha in [(31, orc.DNA), (21, orc.DNA), (33, orc.DNA), (63, orc.DNA5), (96, orc.DNA), (16, orc.DNA16)] + [(k, ALPHA[a]) for k, a in NEW]:
         s = orc.kspec(k, alpha)
         km = rng.integers(0, 1 << 63, size=(64, s.n_words), dtype=np.uint64)
         km[:, -1] &= np.uint64((1 << (64 - (s.n_words * 64 - s.n_bits))) - 1)           # pad bits are zero in a Kmer
