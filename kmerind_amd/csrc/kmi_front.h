@@ -9,8 +9,9 @@
 //
 // Here every WAVEFRONT works a byte range at a time, on its own (no workgroup barrier in the kernel; a large input has four ranges
 // per resident wavefront, and a wavefront takes its next one from a queue word):
-//   produce   64 lanes x 64 bytes: EOL bits only (SWAR), line starts / ends ranked with one DPP scan, their positions into two
-//             small rings in LDS; complete lines get their role from the line index; sequence lines become runs of windows
+//   produce   64 lanes x 64 bytes: EOL bits only (SWAR), line starts / ends ranked with one DPP scan, their positions into a
+//             ring in LDS (line ends alone for an LF text); when 64 complete records wait, one lane per record checks its
+//             markers and lengths (a line's role is its index mod 4) and turns its sequence line into runs of windows
 //   consume   as soon as 64 runs wait: one lane per run loads the read's own bytes, packs THEM (and nothing else) into 2-bit
 //             complement codes -- the run's row, kept for the scatter pass -- and walks the minimizers exactly as
 //             sk_minimizer did (rolling canonical m-mer, order hash, sliding minimum over W positions)
@@ -26,8 +27,21 @@
 namespace kmi {
 
 constexpr int kFrWaves = 4, kFrThreads = kFrWaves * kWave;
-constexpr uint32_t kFrRing = 256;        // line events a wavefront keeps (power of two); a 2 KB step may add half of it
-constexpr uint32_t kFrRunQ = 256;        // waiting runs (power of two): 64 are taken at a time, a step adds at most 128
+constexpr uint32_t kFrRing = 512;        // line-event words a wavefront keeps (power of two): 512 line ends of an LF file, whose line
+                                         // starts follow from them, or 256 (start, end) pairs of any other text
+constexpr uint32_t kFrStepLines = 128;   // lines a produce step may add
+constexpr uint32_t kFrPendEnds = kFrRing - kFrStepLines - 2u, kFrPendPairs = kFrRing / 2u - kFrStepLines;   // waiting lines that leave a step room
+// (A/B knobs, profiles/r12: -DKMI_FR_PASS_RECORDS=1 runs the line pass after every step, -DKMI_FR_PAIRS_ONLY keeps pairs for every text)
+#ifndef KMI_FR_PASS_RECORDS
+#define KMI_FR_PASS_RECORDS 64
+#endif
+constexpr uint32_t kFrPassRecords = KMI_FR_PASS_RECORDS;   // complete records that wait before a line pass runs (1 .. 64)
+#ifdef KMI_FR_PAIRS_ONLY
+constexpr bool kFrEndsOnly = false;
+#else
+constexpr bool kFrEndsOnly = true;
+#endif
+constexpr uint32_t kFrRunQ = 256;       // waiting runs (power of two): 64 are taken at a time, a line pass adds what fits
 constexpr uint32_t kFrStep = 4096;       // bytes per produce step: 64 lanes x 64
 constexpr uint32_t kFrRowDw = 12;        // a run's packed row: 192 bases (a run holds at most 128 + 31)
 constexpr uint32_t kFrNone = 0xffu;      // FrRange::l0 of a range that owns no line
@@ -98,11 +112,14 @@ __global__ __launch_bounds__(kFrThreads) void sk_front_kernel(const uint8_t *__r
   using F = FrCfg<W>;
   constexpr int CAP = kSkListCap;
   constexpr uint32_t INF = 0xffffffffu, RM = kFrRing - 1u, QM = kFrRunQ - 1u;
-  __shared__ uint32_t s_S[kFrWaves][kFrRing], s_E[kFrWaves][kFrRing], s_rq[kFrWaves][kFrRunQ];
+  __shared__ uint32_t s_ring[kFrWaves][kFrRing], s_rq[kFrWaves][kFrRunQ];
   __shared__ uint32_t s_list[kFrWaves][(CAP + 2) * kWave];   // [slot][lane]; slot 0 takes the opening dummy, slot CAP + 1 what does not fit
   __shared__ uint32_t s_hist[kFrWaves][kNumCoarse];
-  const uint32_t lane = lane_id(), wv = wave_id();
-  uint32_t *const S = s_S[wv], *const E = s_E[wv], *const rq = s_rq[wv], *const list = s_list[wv], *const hist = s_hist[wv];
+  // (the wavefront's number as a scalar: from threadIdx.x alone the compiler takes it, the range's number and everything that follows
+  // from them -- positions, counts, every `bail` -- for values that differ between lanes, keeps them in vector registers and masks lanes
+  // where it could branch)
+  const uint32_t lane = lane_id(), wv = (uint32_t)__builtin_amdgcn_readfirstlane((int)wave_id());
+  uint32_t *const Rg = s_ring[wv], *const rq = s_rq[wv], *const list = s_list[wv], *const hist = s_hist[wv];
   auto wave_sync = [&]() { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); __builtin_amdgcn_wave_barrier(); };
   const uint32_t m = k - (uint32_t)W + 1u;
   const uint32_t mmask = (m >= 16u) ? 0xffffffffu : ((1u << (2u * m)) - 1u);
@@ -122,16 +139,26 @@ __global__ __launch_bounds__(kFrThreads) void sk_front_kernel(const uint8_t *__r
   for (uint32_t r = r_first + blockIdx.x * (uint32_t)kFrWaves + wv; r < r_end;) {   // (uniform per wavefront)
     const uint64_t B = (uint64_t)r * range_bytes;
     const uint32_t len = (uint32_t)((n_bytes - B < range_bytes) ? (n_bytes - B) : range_bytes);
-    for (uint32_t i = lane; i < (uint32_t)kNumCoarse; i += kWave) hist[i] = 0;
-    uint32_t why = 0; bool bail = false;                               // this range gives up: the caller takes the general path
     // the range after this one: asked for now, one range ahead (lane 0's atomic; its answer comes in with the byte before the range,
     // which is waited for anyway, and stays in a scalar register)
     uint32_t q_next = 0;
     if (queue && lane == 0) q_next = atomicAdd(queue, 1u);
-    uint32_t carry = (B == 0) ? 1u : (is_eol((uint32_t)__builtin_amdgcn_readfirstlane((int)bytes[B - 1])) ? 1u : 0u);   // EOL status of the byte before the next step
+    const uint32_t carry0 = (B == 0) ? 1u : (is_eol((uint32_t)__builtin_amdgcn_readfirstlane((int)bytes[B - 1])) ? 1u : 0u);
     const uint32_t r_next = queue ? r_first + n_waves + (uint32_t)__builtin_amdgcn_readfirstlane((int)q_next) : r + n_waves;
-    const uint32_t eoff = carry ? 0u : 1u;           // the range starts inside a line: that line's end is not ours
-    uint32_t n_starts = 0, n_ends = 0, n_owned = 0, done = 0, l0 = (r == 0) ? 0u : INF;
+    const uint32_t eoff = carry0 ? 0u : 1u;          // the range starts inside a line: that line's end is not ours
+    // The line events of a range are kept in one of two forms. `simple`: every EOL byte seen so far stood alone (the ordinary LF
+    // file), so a line starts one byte behind its predecessor's end and only the ENDS are written: word e of the ring is end number
+    // e of the range. Otherwise (CRLF, blank lines): (start, end) pairs, line j at words 2 j and 2 j + 1. A range begins as simple,
+    // and the first step that meets an EOL byte behind another one begins the range again in the other form: nothing a range
+    // writes outside its own tables is written before it ends, and a second pass over the same bytes writes the same tables.
+    bool simple = kFrEndsOnly;
+    for (;;) {
+    bool redo = false;
+    for (uint32_t i = lane; i < (uint32_t)kNumCoarse; i += kWave) hist[i] = 0;
+    uint32_t why = 0; bool bail = false;                               // this range gives up: the caller takes the general path
+    uint32_t carry = carry0;                                           // EOL status of the byte before the next step
+    uint32_t n_starts = 0, n_ends = 0, n_owned = 0, done = 0, complete = 0, l0 = (r == 0) ? 0u : INF;
+    bool fin = false;                                // the range's last line is in the ring: no further step
     if (r == 0 && __builtin_amdgcn_readfirstlane((int)bytes[0]) != (int)'@') { why |= 2u; bail = true; }      // (get_next_record refuses a partition that does not begin with '@')
     uint32_t rq_head = 0, rq_tail = 0, run_count = 0, item_count = 0;
     unsigned long long windows = 0;                  // (lane 0's copy counts)
@@ -146,8 +173,9 @@ __global__ __launch_bounds__(kFrThreads) void sk_front_kernel(const uint8_t *__r
       n0 = *reinterpret_cast<const FrU4 *>(q); n1 = *reinterpret_cast<const FrU4 *>(q + 16);
       n2 = *reinterpret_cast<const FrU4 *>(q + 32); n3 = *reinterpret_cast<const FrU4 *>(q + 48);
     }
-    // the first byte of a header / '+' line is loaded when the line completes and compared one step later (nothing waits for it)
-    uint32_t mk_ch = 0, mk_want = 0;
+    uint32_t mk_hd = (uint32_t)'@', mk_plus = (uint32_t)'+';   // the first bytes of the '@' and the '+' line of the last pass's record
+    // where line j of the range starts (j below the lines the ring holds: any value)
+    auto line_start = [&](uint32_t j) -> uint32_t { return simple ? (j + eoff ? Rg[(j + eoff - 1u) & RM] + 1u : 0u) : Rg[(2u * j) & RM]; };
     // EOL bits of 32 bytes: the flags (0x80 per EOL byte) of two dwords gathered into one byte by two dot products with bit
     // weights (the product sits 7 bits too high)
     auto eol32 = [](const FrU4 &a, const FrU4 &b) -> uint32_t {
@@ -163,9 +191,15 @@ __global__ __launch_bounds__(kFrThreads) void sk_front_kernel(const uint8_t *__r
     };
     while (!bail) {
       // ---------------------------------------------------------------- produce
+      // A STEP puts the line events of the next 4 KB into the ring; a LINE PASS takes up to 64 waiting records, one per lane, checks
+      // them and queues their runs. The pass runs when 64 complete records wait or the range's last line is in the ring (and
+      // whenever the ring has no room for another step's lines, which only pairs come to) -- about once in five steps, with every
+      // lane at work, where a pass per step filled 52 lanes of which three in four held a line that makes no run.
       while (producing && rq_tail - rq_head < (uint32_t)kWave && !bail) {
+       if (!fin && !(l0 != INF && ((complete - done + ((l0 + done) & 3u)) >> 2) >= kFrPassRecords) &&
+           n_starts - done <= (simple ? kFrPendEnds : kFrPendPairs)) {
         const uint64_t g = B + p + 64ull * lane;
-        uint32_t eol_lo = 0, eol_hi = 0;
+        uint32_t eol_lo = 0, eol_hi = 0, in_lo = 0xffffffffu, in_hi = 0xffffffffu;   // in_: the bytes that lie inside the buffer
         const FrU4 v0 = n0, v1 = n1, v2 = n2, v3 = n3;
         {
           const uint64_t gn = g + kFrStep;
@@ -179,16 +213,21 @@ __global__ __launch_bounds__(kFrThreads) void sk_front_kernel(const uint8_t *__r
         if (g + 64 <= n_bytes) {
           eol_lo = eol32(v0, v1); eol_hi = eol32(v2, v3);
         } else {
+          in_lo = in_hi = 0;
 #pragma unroll 1
           for (uint32_t i = 0; i < 64u; ++i) {
-            const bool e = (g + i >= n_bytes) || is_eol(bytes[g + i]);   // bytes past the end count as EOL
-            if (i < 32u) eol_lo |= (e ? 1u : 0u) << i; else eol_hi |= (e ? 1u : 0u) << (i - 32u);
+            const bool in = g + i < n_bytes;
+            const bool e = !in || is_eol(bytes[g + i]);   // bytes past the end count as EOL
+            if (i < 32u) { eol_lo |= (e ? 1u : 0u) << i; in_lo |= (in ? 1u : 0u) << i; }
+            else { eol_hi |= (e ? 1u : 0u) << (i - 32u); in_hi |= (in ? 1u : 0u) << (i - 32u); }
           }
         }
         FQ_MARK(1)
         const uint32_t prev = (uint32_t)__builtin_amdgcn_update_dpp((int)carry, (int)(eol_hi >> 31), 0x138 /* wave_shr:1 */, 0xf, 0xf, false);   // lane 0 keeps the carry
         const uint32_t before_lo = (eol_lo << 1) | prev, before_hi = (eol_hi << 1) | (eol_lo >> 31);
-        uint32_t ls_lo = ~eol_lo & before_lo, ls_hi = ~eol_hi & before_hi, le_lo = eol_lo & ~before_lo, le_hi = eol_hi & ~before_hi;
+        // an EOL byte of the buffer behind another EOL byte (the bytes past the buffer's end are not the text's): pairs from here on
+        if (simple && __any(((eol_lo & before_lo & in_lo) | (eol_hi & before_hi & in_hi)) != 0u)) { redo = true; bail = true; break; }
+        const uint32_t ls_lo = ~eol_lo & before_lo, ls_hi = ~eol_hi & before_hi, le_lo = eol_lo & ~before_lo, le_hi = eol_hi & ~before_hi;
         const uint32_t base = p + 64u * lane;
         const uint32_t ns = (uint32_t)__builtin_popcount(ls_lo) + (uint32_t)__builtin_popcount(ls_hi);
         const uint32_t ne = (uint32_t)__builtin_popcount(le_lo) + (uint32_t)__builtin_popcount(le_hi);
@@ -200,12 +239,25 @@ __global__ __launch_bounds__(kFrThreads) void sk_front_kernel(const uint8_t *__r
         const uint32_t inc = wave_inclusive_sum_dpp(packed);
         const uint32_t tot = __builtin_amdgcn_readlane(inc, kWave - 1);
         const uint32_t NS = tot & 1023u, NE = (tot >> 10) & 1023u, NO = tot >> 20;
-        if (NS > kFrRing / 2u || NE > kFrRing / 2u) { why |= 4u; bail = true; break; }
+        if (NS > kFrStepLines || NE > kFrStepLines) { why |= 4u; bail = true; break; }
+        // the events go to the ring: one loop over a lane's 64 bits, left when no lane has an event left (a vote per trip; two trips
+        // for most steps of a text of reads), starts and ends in the same trip
         uint32_t rs = n_starts + ((inc - packed) & 1023u), re = n_ends + (((inc - packed) >> 10) & 1023u);
-        while (ls_lo) { S[rs & RM] = base + (uint32_t)__builtin_ctz(ls_lo); ++rs; ls_lo &= ls_lo - 1u; }
-        while (ls_hi) { S[rs & RM] = base + 32u + (uint32_t)__builtin_ctz(ls_hi); ++rs; ls_hi &= ls_hi - 1u; }
-        while (le_lo) { E[re & RM] = base + (uint32_t)__builtin_ctz(le_lo); ++re; le_lo &= le_lo - 1u; }
-        while (le_hi) { E[re & RM] = base + 32u + (uint32_t)__builtin_ctz(le_hi); ++re; le_hi &= le_hi - 1u; }
+        unsigned long long le = ((unsigned long long)le_hi << 32) | le_lo;
+        if (simple) {
+          while (__any(le != 0ull)) {
+            if (le) { Rg[re & RM] = base + (uint32_t)__builtin_ctzll(le); ++re; le &= le - 1ull; }
+          }
+        } else {
+          unsigned long long ls = ((unsigned long long)ls_hi << 32) | ls_lo;
+          while (__any((ls | le) != 0ull)) {
+            if (ls) { Rg[(2u * rs) & RM] = base + (uint32_t)__builtin_ctzll(ls); ++rs; ls &= ls - 1ull; }
+            if (le) {
+              if (re >= eoff) Rg[(2u * (re - eoff) + 1u) & RM] = base + (uint32_t)__builtin_ctzll(le);   // (end 0 of a range that starts inside a line is not its line's)
+              ++re; le &= le - 1ull;
+            }
+          }
+        }
         n_starts += NS; n_ends += NE; n_owned += NO;
         carry = (uint32_t)__builtin_amdgcn_readlane(eol_hi, kWave - 1) >> 31;   // (the builtin returns a signed int)
         p += kFrStep;
@@ -214,10 +266,10 @@ __global__ __launch_bounds__(kFrThreads) void sk_front_kernel(const uint8_t *__r
         // kFrOverrun bytes behind its end the range gives up and the general path takes the input.
         if (p > len + kFrOverrun) { why |= 32u; bail = true; break; }
         const bool at_eof = B + p > n_bytes;                 // (a step that reached past the end has produced the last line's end)
-        wave_sync();                                         // the events are in the rings
+        wave_sync();                                         // the events are in the ring
         // ---- the line index of the first line (once)
         if (l0 == INF && n_starts > 0u) {
-          if ((uint32_t)__builtin_amdgcn_readfirstlane((int)S[0]) >= len) l0 = kFrNone;                     // the range owns no line: nothing to do here
+          if ((uint32_t)__builtin_amdgcn_readfirstlane((int)line_start(0u)) >= len) l0 = kFrNone;            // the range owns no line: nothing to do here
           else if (at_eof && n_starts < 6u) {
             // the buffer ends here: a well-formed file ends with a quality line, so the lines of this range end on index 3 (mod 4);
             // like every inferred index this one is confirmed by the chain over the ranges
@@ -225,7 +277,7 @@ __global__ __launch_bounds__(kFrThreads) void sk_front_kernel(const uint8_t *__r
           } else if (n_starts >= 6u) {
             const uint32_t nl = 6u;
             uint32_t c = 0;
-            if (lane < nl) c = bytes[B + S[lane]];
+            if (lane < nl) c = bytes[B + line_start(lane)];
             const uint32_t c2 = __shfl_down(c, 2, kWave);
             const bool cand = lane < 4u && lane + 2u < nl && c == (uint32_t)'@' && c2 == (uint32_t)'+';
             const unsigned long long cm = __ballot(cand);
@@ -234,42 +286,76 @@ __global__ __launch_bounds__(kFrThreads) void sk_front_kernel(const uint8_t *__r
           }
         }
         if (l0 == kFrNone) { producing = false; break; }
-        // ---- lines whose end is known: roles, markers, the length rule, runs
-        if (l0 != INF) {
-          const uint32_t complete = n_ends >= eoff ? (n_starts < n_ends - eoff ? n_starts : n_ends - eoff) : 0u;
-          for (uint32_t j0 = done; j0 < complete && !bail; j0 += kWave) {
-            const uint32_t j = j0 + lane;
-            const bool have = j < complete;
-            uint32_t sj = 0, L = 0, role = 4;
-            if (have) { sj = S[j & RM]; L = E[(j + eoff) & RM] - sj; role = (l0 + j) & 3u; }
-            const bool owned = have && sj < len;
-            bool bad = false;
-            if (mk_want && mk_ch != mk_want) bad = true;   // the previous batch's marker
-            mk_want = 0;
-            if (owned && (role == 0u || role == 2u)) { mk_ch = bytes[B + sj]; mk_want = role == 0u ? (uint32_t)'@' : (uint32_t)'+'; }
-            if (have && role == 3u && j >= 2u && S[(j - 2u) & RM] < len) bad = bad || (E[(j - 2u + eoff) & RM] - S[(j - 2u) & RM] != L);
-            if (__any(bad)) {
-              why |= 16u; bail = true; break;
-            }
-            uint32_t nr = 0, nwin = 0;
-            if (owned && role == 1u && L >= k) { nwin = L - k + 1u; nr = (nwin + seg - 1u) / seg; }
-            const uint32_t rinc = wave_inclusive_sum_dpp(nr);
-            const uint32_t rtot = __builtin_amdgcn_readlane(rinc, kWave - 1);
-            if ((rq_tail + rtot - rq_head > kFrRunQ || __any(have && (sj >> 24))) && rtot) { { why |= 32u; bail = true; break; } }   // a long read's many runs, or a range past 16 MB
-            uint32_t o = rq_tail + rinc - nr;
+        if (l0 == INF) {                                     // (fewer than six line starts so far)
+          if (at_eof) producing = false;
+          wave_sync();
+          continue;
+        }
+        complete = n_ends >= eoff ? (n_starts < n_ends - eoff ? n_starts : n_ends - eoff) : 0u;   // lines whose end is known
+        // the last step: the range is scanned and the two lines behind its last one are complete (their quality lines are checked here)
+        fin = at_eof || (p >= len && complete >= n_owned + 2u);
+       }
+        // ---- the line pass: lane i takes the record whose '@' line is line jb + 4 i of the range -- markers, the length rule, runs.
+        // A line belongs to the range where it starts: the first record of a range may lack its first lines (l0 of them belong to
+        // the range before: the lines below `done` = 0), the records behind the range's end are looked at for the length rule alone,
+        // and that rule looks two lines back only if that line is owned.
+        const uint32_t jb = done - ((l0 + done) & 3u);       // (below zero, i.e. wrapped, for a first record that lacks lines)
+        const uint32_t whole = (complete - jb) >> 2;         // complete records that wait
+        if (!fin && whole < kFrPassRecords && n_starts - done <= (simple ? kFrPendEnds : kFrPendPairs)) { wave_sync(); continue; }
+        if (fin && done == complete) { producing = false; break; }
+        const uint32_t ahead = fin ? complete - jb : 4u * whole;                       // lines from jb on that may be worked ...
+        const uint32_t lim = jb + (ahead < 4u * kWave ? ahead : 4u * kWave);          // ... in this pass: those below lim
+        const uint32_t n_rec = (lim - jb + 3u) >> 2;
+        if (n_rec == 0u) { why |= 32u; bail = true; break; }   // (not reached: without room for a step the ring holds 31 records and more)
+        {
+          const uint32_t jr = jb + 4u * lane;
+          const bool in_pass = lane < n_rec;
+          uint32_t s[4], e[4];
+          bool v[4];
+#pragma unroll
+          for (uint32_t t = 0; t < 4u; ++t) v[t] = in_pass && (int32_t)(jr + t - done) >= 0 && (int32_t)(lim - (jr + t)) > 0;
+          if (simple) {   // (uniform) five ends: a line starts behind the end before it; line 0 of a range that begins a line, at 0
+            uint32_t x[5];
+#pragma unroll
+            for (uint32_t t = 0; t < 5u; ++t) x[t] = Rg[(jr + eoff - 1u + t) & RM];
+#pragma unroll
+            for (uint32_t t = 0; t < 4u; ++t) { s[t] = (jr + t + eoff) ? x[t] + 1u : 0u; e[t] = x[t + 1u]; }
+          } else {
+#pragma unroll
+            for (uint32_t t = 0; t < 4u; ++t) { s[t] = Rg[(2u * (jr + t)) & RM]; e[t] = Rg[(2u * (jr + t) + 1u) & RM]; }
+          }
+          const bool own_hd = v[0] && s[0] < len, own_seq = v[1] && s[1] < len, own_plus = v[2] && s[2] < len;
+          // the record's two marker bytes: two loads issued together, compared by the pass after this one (nothing waits for them)
+          bool bad = mk_hd != (uint32_t)'@' || mk_plus != (uint32_t)'+';
+          mk_hd = (uint32_t)'@'; mk_plus = (uint32_t)'+';
+          if (own_hd) mk_hd = bytes[B + s[0]];
+          if (own_plus) mk_plus = bytes[B + s[2]];
+          const uint32_t L = e[1] - s[1];
+          if (v[3] && own_seq) bad = bad || (e[3] - s[3] != L);   // (a quality line that is worked has its sequence line in the same pass)
+          if (__any(bad)) { why |= 16u; bail = true; break; }
+          uint32_t nr = 0, nwin = 0;
+          if (own_seq && L >= k) { nwin = L - k + 1u; nr = (nwin + seg - 1u) / seg; }
+          // the records whose runs the queue has room for (a prefix of the lanes: the sums only grow); the others wait for the next
+          // pass, after a batch of runs has left the queue
+          const uint32_t rinc = wave_inclusive_sum_dpp(nr);
+          const uint32_t n_fit = (uint32_t)__popcll(__ballot(in_pass && rinc <= kFrRunQ - (rq_tail - rq_head)));
+          // a record with more runs than the queue has room for beside 63 waiting ones (a long read), or a range past 16 MB
+          if (n_fit == 0u || __any(nr && (s[1] >> 24))) { why |= 32u; bail = true; break; }
+          if (lane < n_fit) {
+            const uint32_t o = rq_tail + rinc - nr;
             for (uint32_t i = 0; i < nr; ++i) {
               const uint32_t left = nwin - i * seg;
-              rq[(o + i) & QM] = (sj + i * seg) | (((left < seg ? left : seg) - 1u) << 24);
+              rq[(o + i) & QM] = (s[1] + i * seg) | (((left < seg ? left : seg) - 1u) << 24);
             }
-            rq_tail += rtot;
           }
-          if (bail) break;
-          done = complete;
-          // done when the range is scanned and the two lines behind its last one are complete (their quality lines are checked here)
-          if (at_eof || (p >= len && complete >= n_owned + 2u)) producing = false;
-        } else if (at_eof) { producing = false; }   // (no line start at all)
-        wave_sync();                                         // the queue is written; the rings may be overwritten by the next step
+          rq_tail += (uint32_t)__builtin_amdgcn_readlane((int)rinc, (int)(n_fit - 1u));
+          done = n_fit == n_rec ? lim : jb + 4u * n_fit;
+        }
+        if (fin && done == complete) producing = false;
+        wave_sync();                                         // the queue is written; the ring may be overwritten by the next step
+        FQ_MARK(2)
       }
+      if (redo) break;
       if (bail) break;
       FQ_MARK(2)
       // ---------------------------------------------------------------- consume
@@ -536,7 +622,8 @@ __global__ __launch_bounds__(kFrThreads) void sk_front_kernel(const uint8_t *__r
       wave_sync();   // the list is read; the next batch overwrites it
       FQ_MARK(6)
     }
-    if (!bail && __any(mk_want && mk_ch != mk_want)) { why |= 16u; bail = true; }   // the last batch's markers
+    if (redo) { simple = false; wave_sync(); continue; }   // once more, with (start, end) pairs
+    if (!bail && __any(mk_hd != (uint32_t)'@' || mk_plus != (uint32_t)'+')) { why |= 16u; bail = true; }   // the last pass's markers
     if (bail) { if (lane == 0) { atomicOr(&flags[FLAG_SK_DECLINED], 4u); atomicOr(&flags[FLAG_SK_WHY], why); } }
     wave_sync();
     if (lane == 0) {
@@ -551,6 +638,8 @@ __global__ __launch_bounds__(kFrThreads) void sk_front_kernel(const uint8_t *__r
     }
     wave_sync();
     FQ_MARK(7)
+    break;
+    }
     r = r_next;
   }
 #ifdef KMI_FR_TIMING
