@@ -266,7 +266,9 @@ kmi_status kmi_index_build_dev(kmi_index *idx, const uint8_t *bytes_dev, size_t 
 /* MapType::clear() (distributed_map_base.hpp:267-272) */
 kmi_status kmi_index_clear(kmi_index *idx);
 /* The SeqParser template argument of Index::build_posix / build_mmap / build_mpiio<SeqParser, SeqIterType>
- * (kmer_index.hpp:239-372): which record grammar the next kmi_index_build_* call parses (KMI_FMT_*). */
+ * (kmer_index.hpp:239-372): which record grammar the next kmi_index_build_* call parses (KMI_FMT_*). A position + quality index
+ * reads FASTQ only: KMI_FMT_FASTA gives KMI_ERR_INVALID there and leaves the format as it was (so does kmi_index_create with such
+ * a configuration). */
 kmi_status kmi_index_set_seq_format(kmi_index *idx, uint32_t seq_format);
 /* the SeqIterType template argument of Index::build_* (kmer_index.hpp:239-372): KMI_SEQ_* for the following builds */
 kmi_status kmi_index_set_seq_filter(kmi_index *idx, uint32_t seq_filter);

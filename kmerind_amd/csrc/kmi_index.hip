@@ -3762,6 +3762,7 @@ kmi_status kmi_index_create(kmi_ctx *ctx, const kmi_config *cfg, kmi_index **out
   if (!ctx || !out) return KMI_ERR_INVALID;
   KShape shape;
   if (!valid_config(cfg, &shape)) return set_err(ctx, KMI_ERR_INVALID, "bad kmi_config");
+  if (cfg->index_kind == KMI_INDEX_POSQUAL && cfg->seq_format != KMI_FMT_FASTQ) return set_err(ctx, KMI_ERR_INVALID, "quality values need FASTQ input");
   kmi_index *idx = new kmi_index();
   idx->ctx = ctx; idx->cfg = *cfg; idx->shape = shape;
   idx->val_words = cfg->index_kind == KMI_INDEX_COUNT ? 0u : (cfg->index_kind == KMI_INDEX_POSITION ? 1u : 2u);
@@ -3830,6 +3831,8 @@ kmi_status kmi_index_insert_host(kmi_index *idx, const uint64_t *kmers, size_t n
 kmi_status kmi_index_set_seq_format(kmi_index *idx, uint32_t seq_format) {
   if (!idx) return KMI_ERR_INVALID;
   if (seq_format > KMI_FMT_FASTA) return set_err(idx->ctx, KMI_ERR_INVALID, "unknown sequence format");
+  // (as kmi_extract_records_dev and the builds over ranks: a FASTA record has no quality line to take the second value word from)
+  if (idx->cfg.index_kind == KMI_INDEX_POSQUAL && seq_format != KMI_FMT_FASTQ) return set_err(idx->ctx, KMI_ERR_INVALID, "quality values need FASTQ input");
   idx->cfg.seq_format = seq_format;
   return KMI_OK;
 }

@@ -146,8 +146,10 @@ def test_all_ones_key_and_heavy_hitter(ctx):
 
 
 def test_many_distinct_keys_multi_pass_buckets(ctx):
-    """3M distinct keys -> ~92 per fine bucket is easy; force table overflow with 40M? no: use a
-    skewed set where one fine bucket gets > table capacity distinct keys."""
+    """3M random distinct keys, about 92 per fine bucket: many buckets, none of which needs a second pass (the name is older
+    than the tests that do force passes: test_bucket_with_more_distinct_keys_than_the_lds_table_takes_more_passes below,
+    test_gpu_shape_matrix.py::test_one_fine_bucket_fuller_than_a_tagged_table for multi-word keys, and
+    test_gpu_position_sequences.py::test_query_passes_on_a_multimap for the position indexes)."""
     import kmerind_amd as K
     from kmerind_amd import core
     cfg = K.make_config(31, "DNA", strand="single")
