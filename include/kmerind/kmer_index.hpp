@@ -730,6 +730,49 @@ class Index {
     out.resize((size_t)n);
     return out;
   }
+  // Position indexes on one rank. locate: occ[i] = entries under query[i]'s transformed key; values[offsets[i] .. offsets[i + 1]) =
+  // their values when occ[i] <= max_occ, nothing otherwise (a key is listed whole or not at all); one answer per query, in query
+  // order. Under the canonical strand model a hit does not tell the orientation of the reference occurrence.
+  struct Located { std::vector<uint32_t> occ; std::vector<uint64_t> offsets; std::vector<ValueType> values; };
+  Located locate(std::vector<KmerType> const &query, uint32_t max_occ = KMI_LOCATE_ALL) const {
+    static_assert(MapType::index_kind != KMI_INDEX_COUNT, "locate() is a member of the position indexes");
+    if (comm.size() > 1) throw std::invalid_argument("locate() answers from one rank's entries: size() > 1 is not supported");
+    constexpr unsigned vw = detail::stored_words<MapType, ValueType>();
+    Located out;
+    out.occ.resize(query.size());
+    out.offsets.resize(query.size() + 1);
+    uint64_t n = 0;
+    ::kmerind::check(ctx, kmi_index_locate_host(idx, detail::words_of(query), query.size(), max_occ, out.occ.data(), out.offsets.data(), nullptr, 0, &n));
+    std::vector<uint64_t> words((size_t)n * vw);
+    if (n) ::kmerind::check(ctx, kmi_index_locate_host(idx, detail::words_of(query), query.size(), max_occ, out.occ.data(), out.offsets.data(), words.data(), (size_t)n, &n));
+    out.values.resize((size_t)n);
+    for (uint64_t i = 0; i < n; ++i) out.values[i] = detail::stored_value<MapType, ValueType>(&words[i * vw]);
+    return out;
+  }
+  // seed_reads: locate for every window of every read of a FASTQ file, in file order. Window j of read r is query
+  // reads[r].first_kmer + j of (occ, offsets, values). The file is read as build_posix reads it, and always parsed as FASTQ,
+  // whatever the index was built from.
+  struct Seeds { std::vector<kmi_read_seeds> reads; std::vector<uint32_t> occ; std::vector<uint64_t> offsets; std::vector<ValueType> values; };
+  Seeds seed_reads(const std::string &fastq, uint32_t max_occ = KMI_LOCATE_ALL) const {
+    static_assert(MapType::index_kind != KMI_INDEX_COUNT, "seed_reads() is a member of the position indexes");
+    if (comm.size() > 1) throw std::invalid_argument("seed_reads() answers from one rank's entries: size() > 1 is not supported");
+    if (detail::format_of(fastq) != KMI_FMT_FASTQ) throw std::invalid_argument("seed_reads() reads FASTQ files");
+    constexpr unsigned vw = detail::stored_words<MapType, ValueType>();
+    const std::vector<uint8_t> bytes = detail::read_whole_file(fastq);
+    uint64_t nr = 0, nk = 0, nh = 0;
+    ::kmerind::check(ctx, kmi_index_seed_reads_host(idx, bytes.data(), bytes.size(), max_occ, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, &nr, &nk, &nh));
+    Seeds out;
+    out.reads.resize((size_t)nr);
+    out.occ.resize((size_t)nk);
+    out.offsets.resize((size_t)nk + 1);
+    std::vector<uint64_t> words((size_t)nh * vw);
+    ::kmerind::check(ctx, kmi_index_seed_reads_host(idx, bytes.data(), bytes.size(), max_occ, nr ? out.reads.data() : nullptr, (size_t)nr,
+                                                    nk ? out.occ.data() : nullptr, out.offsets.data(), (size_t)nk, nh ? words.data() : nullptr, (size_t)nh,
+                                                    &nr, &nk, &nh));
+    out.values.resize((size_t)nh);
+    for (uint64_t i = 0; i < nh; ++i) out.values[i] = detail::stored_value<MapType, ValueType>(&words[i * vw]);
+    return out;
+  }
 
   // ---- the count spectrum and the filter by count, on the device (erase_if(pred) stays the route for any other predicate).
   // count_spectrum: out[min(count, n_bins - 1)] = number of stored keys with that count, over all ranks (collective when size() > 1).

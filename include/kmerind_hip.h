@@ -99,8 +99,8 @@ kmi_status kmi_ctx_reset_hints(kmi_ctx *ctx);
  * enlarge its receive pool (kmi_index_build_dist_dev); 1: microseconds this context has spent inside hipMalloc / hipFree; 2: bytes
  * and 3: calls that reached hipMalloc; 4: blocks taken from the process-wide cache instead; 5: pointer-jumping rounds, 6: exchanges
  * and 7: bytes this rank sent in the context's last kmi_dbg_compact_dist_host; 8: the largest number of passes a bucket needed in
- * the context's last kmi_index_lookup_* / kmi_index_profile_reads_* (1 when every bucket's entries fit one table; 0: no bucket was
- * looked at); 9: the entry count of the fullest bucket the context's last kmi_index_retain_counts met (0: the index was empty);
+ * the context's last kmi_index_lookup_* / kmi_index_profile_reads_* / kmi_index_locate_* / kmi_index_seed_reads_* (1 when every
+ * bucket's entries fit one table; 0: no bucket was looked at); 9: the entry count of the fullest bucket the context's last kmi_index_retain_counts met (0: the index was empty);
  * 10: the largest number of passes a bucket needed in the context's last kmi_index_compare* / kmi_index_combine (0: no bucket
  * was looked at) */
 kmi_status kmi_ctx_debug_counter(const kmi_ctx *ctx, uint32_t which, uint64_t *value);
@@ -486,6 +486,64 @@ kmi_status kmi_index_profile_reads_dev (kmi_index *idx, const uint8_t *bytes_dev
                                         kmi_read_profile *out_dev, size_t capacity, uint64_t *n_reads);
 kmi_status kmi_index_profile_reads_host(kmi_index *idx, const uint8_t *bytes, size_t n_bytes, uint32_t solid_threshold,
                                         kmi_read_profile *out, size_t capacity, uint64_t *n_reads);
+
+/* ---- the position indexes in the caller's order: where does each k-mer occur, and the seeds of reads (no counterpart in the
+ * reference: its find() returns the (key, value) pairs of the distinct queried keys in no particular order, and it has no cap on
+ * repetitive keys and no per-read query)
+ * Position and position + quality indexes only (KMI_INDEX_POSITION, KMI_INDEX_POSQUAL); a count index gives KMI_ERR_INVALID. Every
+ * key shape these indexes take (one to four words). One rank's entries only, as for lookup. The index is never changed.
+ * Strand. Under the canonical strand model a hit does not tell the orientation of the reference occurrence relative to the query:
+ * the index stores the canonical k-mer and the position, not which strand of the reference spelled it.
+ *
+ * locate:
+ *   occ[i]     = number of index entries whose key is InputTransform(queries[i]) (the true multiplicity, never capped)
+ *   listed(i)  = occ[i] if occ[i] <= max_occ, else 0 (a key is listed whole or not at all)
+ *   offsets[i] = sum of listed(j), j < i; offsets[nq] = *n_hits
+ *   values[offsets[i] .. offsets[i+1]) = the value words (1 per hit for POSITION, 2 for POSQUAL) of those entries: one answer per
+ *                query in query order, a key asked twice is answered twice. The order of the hits inside one query is unspecified.
+ *  - max_occ == 0 gives KMI_ERR_INVALID; KMI_LOCATE_ALL means no cap.
+ *  - nq == 0 is fine: offsets[0] = 0, *n_hits = 0, no other buffer is touched. An empty index answers occ = 0 everywhere.
+ *  - occ, offsets and *n_hits are always written in full. capacity (in hits) < *n_hits gives KMI_ERR_OVERFLOW and nothing is written
+ *    into values. values == NULL with capacity == 0 is the sizing call: KMI_OK, and the fill pass is skipped.
+ *  - KMI_ERR_OVERFLOW with the message of the other queries when a bucket cannot be handled within the pass limit.
+ * kmi_ctx_debug_counter 8 tells the largest pass count of the call; KMI_LOOKUP_CAP shrinks these tables too. */
+enum { KMI_LOCATE_ALL = 0xffffffffu };   /* max_occ: no cap */
+kmi_status kmi_index_locate_dev (kmi_index *idx, const uint64_t *queries_dev, size_t nq, uint32_t max_occ,
+                                 uint32_t *occ_dev /* nq */, uint64_t *offsets_dev /* nq + 1 */,
+                                 uint64_t *values_dev, size_t capacity /* hits */, uint64_t *n_hits);
+kmi_status kmi_index_locate_host(kmi_index *idx, const uint64_t *queries, size_t nq, uint32_t max_occ,
+                                 uint32_t *occ /* nq */, uint64_t *offsets /* nq + 1 */,
+                                 uint64_t *values, size_t capacity /* hits */, uint64_t *n_hits);
+
+typedef struct {
+  uint64_t seq_offset;  /* as kmi_read_profile.seq_offset */
+  uint64_t first_kmer;  /* index of the read's first window in occ[] / offsets[] (for a read without a window: where it would be) */
+  uint32_t n_kmers;     /* windows of the read (KMI_SEQ_ALL) */
+  uint32_t n_listed;    /* of those, with at least one listed hit */
+  uint64_t n_hits;      /* offsets[first_kmer + n_kmers] - offsets[first_kmer] */
+} kmi_read_seeds;       /* 32 bytes */
+
+/* seed_reads: locate for every window of every read of a FASTQ buffer, the seed stage of read mapping.
+ *  - Rows. One row per FASTQ record of the record-aligned buffer, in file order, records without a k-mer included.
+ *  - Windows. Exactly those of kmi_extract_dev with the index's k, alphabet and strand transform and KMI_SEQ_ALL. Window j of read r
+ *    is query rows[r].first_kmer + j of one CSR (occ, offsets, values) over all windows of the buffer, with locate's meaning.
+ *  - Format. The reads are always parsed as FASTQ, whatever the index was built from (a FASTA-built index questioned with FASTQ
+ *    reads is the expected case). Malformed input gives KMI_ERR_PARSE. The 65535-byte in-record limit applies as for profile_reads.
+ *  - Capacities. *n_reads, *n_kmers and *n_hits are always exact. If any capacity is short the call returns KMI_ERR_OVERFLOW;
+ *    nothing is written past any capacity and the buffers' contents are otherwise unspecified. offsets takes cap_kmers + 1 words.
+ *    All buffers NULL with zero capacities is the sizing call: KMI_OK, only the counting passes run.
+ *  - max_occ == 0 gives KMI_ERR_INVALID. n_bytes == 0 is fine (offsets[0] = 0 when offsets is given).
+ *  - Batches. Record-aligned batches of at most KMI_PROFILE_BATCH bytes, as for profile_reads; the results do not depend on it. */
+kmi_status kmi_index_seed_reads_dev (kmi_index *idx, const uint8_t *bytes_dev, size_t n_bytes, uint32_t max_occ,
+                                     kmi_read_seeds *rows_dev, size_t cap_reads,
+                                     uint32_t *occ_dev, uint64_t *offsets_dev /* cap_kmers + 1 */, size_t cap_kmers,
+                                     uint64_t *values_dev, size_t cap_hits,
+                                     uint64_t *n_reads, uint64_t *n_kmers, uint64_t *n_hits);
+kmi_status kmi_index_seed_reads_host(kmi_index *idx, const uint8_t *bytes, size_t n_bytes, uint32_t max_occ,
+                                     kmi_read_seeds *rows, size_t cap_reads,
+                                     uint32_t *occ, uint64_t *offsets /* cap_kmers + 1 */, size_t cap_kmers,
+                                     uint64_t *values, size_t cap_hits,
+                                     uint64_t *n_reads, uint64_t *n_kmers, uint64_t *n_hits);
 
 /* ---- the count spectrum, and the filter by count (no counterpart in the reference beyond to_vector() plus a host loop, the way
  * its erase_if(pred) works)

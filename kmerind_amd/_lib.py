@@ -24,6 +24,7 @@ FMT_FASTQ, FMT_FASTA = 0, 1
 INDEX_COUNT, INDEX_POSITION, INDEX_POSQUAL = 0, 1, 2
 SEQ_ALL, SEQ_N_FILTER, SEQ_N_SPLIT = 0, 1, 2
 DIST_MODEL, DIST_LEX, DIST_XOR = 0, 1, 2
+LOCATE_ALL = 0xFFFFFFFF   # max_occ of locate / seed_reads: no cap
 
 
 class FastaPartition(C.Structure):
@@ -165,6 +166,10 @@ SIGNATURES = {
     "kmi_index_lookup_host": (C.c_int, [_P, _P, _sz, _P]),
     "kmi_index_profile_reads_dev": (C.c_int, [_P, _P, _sz, _u32, _P, _sz, C.POINTER(_u64)]),
     "kmi_index_profile_reads_host": (C.c_int, [_P, _P, _sz, _u32, _P, _sz, C.POINTER(_u64)]),
+    "kmi_index_locate_dev": (C.c_int, [_P, _P, _sz, _u32, _P, _P, _P, _sz, C.POINTER(_u64)]),
+    "kmi_index_locate_host": (C.c_int, [_P, _P, _sz, _u32, _P, _P, _P, _sz, C.POINTER(_u64)]),
+    "kmi_index_seed_reads_dev": (C.c_int, [_P, _P, _sz, _u32, _P, _sz, _P, _P, _sz, _P, _sz, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "kmi_index_seed_reads_host": (C.c_int, [_P, _P, _sz, _u32, _P, _sz, _P, _P, _sz, _P, _sz, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
     "kmi_index_spectrum_dev": (C.c_int, [_P, _u32, _P, C.POINTER(SpectrumTotals)]),
     "kmi_index_spectrum_host": (C.c_int, [_P, _u32, _P, C.POINTER(SpectrumTotals)]),
     "kmi_index_spectrum_dist_host": (C.c_int, [_P, _P, _u32, _P, C.POINTER(SpectrumTotals)]),

@@ -190,6 +190,10 @@ class Context:
 READ_PROFILE_DTYPE = np.dtype([("seq_offset", np.uint64), ("sum_counts", np.uint64), ("n_kmers", np.uint32), ("n_present", np.uint32),
                                ("n_solid", np.uint32), ("lowest", np.uint32), ("highest", np.uint32), ("reserved", np.uint32)])
 assert READ_PROFILE_DTYPE.itemsize == 40
+# kmi_read_seeds (kmerind_hip.h), field for field: 32 bytes per read
+READ_SEEDS_DTYPE = np.dtype([("seq_offset", np.uint64), ("first_kmer", np.uint64), ("n_kmers", np.uint32), ("n_listed", np.uint32),
+                             ("n_hits", np.uint64)])
+assert READ_SEEDS_DTYPE.itemsize == 32
 
 
 def num_buckets():
@@ -468,6 +472,76 @@ class PositionIndex(CountIndex):
     def count(self, q):
         keys, vals = self._query(lib.kmi_index_count_host, q)
         return keys, vals[:, 0]
+
+    # ---- queries in the caller's order (kmi_index_locate_* / kmi_index_seed_reads_*; no reference counterpart)
+    def _raise(self, st, **totals):
+        err = L.KmiError(st, (lib.kmi_last_error(self.ctx.h) or b"").decode())
+        for name, v in totals.items():
+            setattr(err, name, v)
+        raise err
+
+    def locate(self, q, max_occ=None):
+        """(occ, offsets, values): occ[i] = entries under the transformed q[i]; values[offsets[i]:offsets[i + 1]] = their value
+        rows (shape (n_hits, value_words)) when occ[i] <= max_occ, nothing otherwise. One answer per query, in query order."""
+        q = _u64(q, self.n_words)
+        nq = q.shape[0]
+        max_occ = L.LOCATE_ALL if max_occ is None else int(max_occ)
+        occ = np.zeros(nq, dtype=np.uint32)
+        offsets = np.zeros(nq + 1, dtype=np.uint64)
+        n = C.c_uint64()
+        args = (self.h, q.ctypes.data_as(C.c_void_p), nq, max_occ, occ.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p))
+        self.ctx.check(lib.kmi_index_locate_host(*args, None, 0, C.byref(n)))   # the sizing call
+        values = np.zeros((n.value, self.value_words), dtype=np.uint64)
+        if n.value:
+            self.ctx.check(lib.kmi_index_locate_host(*args, values.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+        return occ, offsets, values
+
+    def locate_device(self, q_dptr, n, occ_dptr, offsets_dptr, values_dptr=0, capacity=0, max_occ=None):
+        """q_dptr: n k-mers on the device; occ_dptr: n u32; offsets_dptr: n + 1 u64; values_dptr: room for `capacity` hits of
+        value_words u64 (0 with capacity 0: the sizing call) -> number of listed hits"""
+        max_occ = L.LOCATE_ALL if max_occ is None else int(max_occ)
+        hits = C.c_uint64()
+        st = lib.kmi_index_locate_dev(self.h, C.c_void_p(q_dptr), n, max_occ, C.c_void_p(occ_dptr), C.c_void_p(offsets_dptr),
+                                      C.c_void_p(values_dptr) if values_dptr else None, capacity, C.byref(hits))
+        if st != L.OK:
+            self._raise(st, n_hits=hits.value)
+        return hits.value
+
+    def seed_reads(self, data, max_occ=None):
+        """(rows, occ, offsets, values): one row (READ_SEEDS_DTYPE) per FASTQ record of `data`, in file order; window j of read r
+        is query rows[r]['first_kmer'] + j of the locate() arrays over all windows of the buffer"""
+        buf = np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else \
+            np.ascontiguousarray(data, dtype=np.uint8)
+        max_occ = L.LOCATE_ALL if max_occ is None else int(max_occ)
+        nr, nk, nh = C.c_uint64(), C.c_uint64(), C.c_uint64()
+        tail = (C.byref(nr), C.byref(nk), C.byref(nh))
+        head = (self.h, buf.ctypes.data_as(C.c_void_p), buf.size, max_occ)
+        self.ctx.check(lib.kmi_index_seed_reads_host(*head, None, 0, None, None, 0, None, 0, *tail))   # the sizing call
+        rows = np.zeros(nr.value, dtype=READ_SEEDS_DTYPE)
+        occ = np.zeros(nk.value, dtype=np.uint32)
+        offsets = np.zeros(nk.value + 1, dtype=np.uint64)
+        values = np.zeros((nh.value, self.value_words), dtype=np.uint64)
+
+        def ptr(a):
+            return a.ctypes.data_as(C.c_void_p) if a.size else None
+        self.ctx.check(lib.kmi_index_seed_reads_host(*head, ptr(rows), rows.size, ptr(occ), offsets.ctypes.data_as(C.c_void_p), occ.size,
+                                                     ptr(values), values.shape[0], *tail))
+        return rows, occ, offsets, values
+
+    def seed_reads_device(self, dptr, nbytes, rows_dptr=0, cap_reads=0, occ_dptr=0, offsets_dptr=0, cap_kmers=0, values_dptr=0, cap_hits=0,
+                          max_occ=None):
+        """dptr: FASTQ bytes on the device; rows_dptr: room for cap_reads rows of 32 bytes; occ_dptr: cap_kmers u32; offsets_dptr:
+        cap_kmers + 1 u64; values_dptr: cap_hits hits of value_words u64 (all 0: the sizing call) -> (n_reads, n_kmers, n_hits)"""
+        max_occ = L.LOCATE_ALL if max_occ is None else int(max_occ)
+        nr, nk, nh = C.c_uint64(), C.c_uint64(), C.c_uint64()
+
+        def ptr(p):
+            return C.c_void_p(p) if p else None
+        st = lib.kmi_index_seed_reads_dev(self.h, C.c_void_p(dptr), nbytes, max_occ, ptr(rows_dptr), cap_reads, ptr(occ_dptr), ptr(offsets_dptr),
+                                          cap_kmers, ptr(values_dptr), cap_hits, C.byref(nr), C.byref(nk), C.byref(nh))
+        if st != L.OK:
+            self._raise(st, n_reads=nr.value, n_kmers=nk.value, n_hits=nh.value)
+        return nr.value, nk.value, nh.value
 
 
 class DeBruijnNodes:

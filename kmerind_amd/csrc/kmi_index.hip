@@ -3674,6 +3674,7 @@ static kmi_status merge_impl(kmi_index *idx, uint32_t nparts, const uint64_t *ke
 #include "kmi_unitig_dist.h"
 #include "kmi_update.h"
 #include "kmi_lookup.h"
+#include "kmi_locate.h"
 #include "kmi_spectrum.h"
 #include "kmi_setops.h"
 
@@ -5317,6 +5318,71 @@ kmi_status kmi_index_profile_reads_dev(kmi_index *idx, const uint8_t *bytes_dev,
 kmi_status kmi_index_profile_reads_host(kmi_index *idx, const uint8_t *bytes, size_t n_bytes, uint32_t solid_threshold, kmi_read_profile *out,
                                         size_t capacity, uint64_t *n_reads) {
   return profile_reads_entry(idx, bytes, n_bytes, false, solid_threshold, out, capacity, n_reads);
+}
+
+// ---- the position indexes in the caller's order (kmi_locate.h)
+kmi_status kmi_index_locate_dev(kmi_index *idx, const uint64_t *queries_dev, size_t nq, uint32_t max_occ, uint32_t *occ_dev, uint64_t *offsets_dev,
+                                uint64_t *values_dev, size_t capacity, uint64_t *n_hits) {
+  if (!idx || !n_hits) return KMI_ERR_INVALID;
+  kmi_ctx *ctx = idx->ctx;
+  *n_hits = 0;
+  if (!idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "locate() is a member of the position indexes");
+  if (max_occ == 0) return set_err(ctx, KMI_ERR_INVALID, "max_occ is at least 1");
+  if (!offsets_dev || (nq && (!queries_dev || !occ_dev)) || (!values_dev && capacity)) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
+  KMI_HIP(ctx, hipSetDevice(ctx->device));
+  return index_locate(idx, queries_dev, nq, max_occ, occ_dev, offsets_dev, values_dev, capacity, n_hits);
+}
+
+kmi_status kmi_index_locate_host(kmi_index *idx, const uint64_t *queries, size_t nq, uint32_t max_occ, uint32_t *occ, uint64_t *offsets,
+                                 uint64_t *values, size_t capacity, uint64_t *n_hits) {
+  if (!idx || !n_hits) return KMI_ERR_INVALID;
+  kmi_ctx *ctx = idx->ctx;
+  *n_hits = 0;
+  if (!idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "locate() is a member of the position indexes");
+  if (max_occ == 0) return set_err(ctx, KMI_ERR_INVALID, "max_occ is at least 1");
+  if (!offsets || (nq && (!queries || !occ)) || (!values && capacity)) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
+  KMI_HIP(ctx, hipSetDevice(ctx->device));
+  void *dq, *dc, *dof, *dv = nullptr;
+  const size_t q_bytes = nq * idx->shape.n_words * sizeof(uint64_t), v_bytes = capacity * idx->val_words * sizeof(uint64_t);
+  KMI_TRY(ws_get(ctx, WS_INPUT, q_bytes, &dq));
+  KMI_TRY(ws_get(ctx, WS_LOOKUP_CNT, nq * sizeof(uint32_t), &dc));
+  KMI_TRY(ws_get(ctx, WS_LOCATE_OFF, (nq + 1) * sizeof(uint64_t), &dof));
+  if (values) KMI_TRY(ws_get(ctx, WS_OUTPUT2, v_bytes, &dv));
+  if (nq) KMI_HIP(ctx, hipMemcpyAsync(dq, queries, q_bytes, hipMemcpyHostToDevice, ctx->stream));
+  const kmi_status st = index_locate(idx, (const uint64_t *)dq, nq, max_occ, (uint32_t *)dc, (uint64_t *)dof, (uint64_t *)dv, capacity, n_hits);
+  if (st != KMI_OK && !(st == KMI_ERR_OVERFLOW && *n_hits > capacity)) return st;
+  // (occ and offsets are complete when only the capacity was short)
+  if (nq) KMI_HIP(ctx, hipMemcpyAsync(occ, dc, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  KMI_HIP(ctx, hipMemcpyAsync(offsets, dof, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (st == KMI_OK && values && *n_hits)
+    KMI_HIP(ctx, hipMemcpyAsync(values, dv, *n_hits * idx->val_words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return st;
+}
+
+static kmi_status seed_reads_entry(kmi_index *idx, const uint8_t *bytes, size_t n_bytes, bool on_device, uint32_t max_occ, kmi_read_seeds *rows,
+                                   size_t cap_reads, uint32_t *occ, uint64_t *offsets, size_t cap_kmers, uint64_t *values, size_t cap_hits,
+                                   uint64_t *n_reads, uint64_t *n_kmers, uint64_t *n_hits) {
+  if (!idx || !n_reads || !n_kmers || !n_hits) return KMI_ERR_INVALID;
+  kmi_ctx *ctx = idx->ctx;
+  *n_reads = *n_kmers = *n_hits = 0;
+  if (!idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "seed_reads() is a member of the position indexes");
+  if (max_occ == 0) return set_err(ctx, KMI_ERR_INVALID, "max_occ is at least 1");
+  if ((n_bytes && !bytes) || (!rows && cap_reads) || ((!occ || !offsets) && cap_kmers) || (!values && cap_hits))
+    return set_err(ctx, KMI_ERR_INVALID, "null buffer");
+  KMI_HIP(ctx, hipSetDevice(ctx->device));
+  return index_seed_reads(idx, bytes, n_bytes, on_device, max_occ, rows, cap_reads, occ, offsets, cap_kmers, values, cap_hits, n_reads, n_kmers, n_hits);
+}
+kmi_status kmi_index_seed_reads_dev(kmi_index *idx, const uint8_t *bytes_dev, size_t n_bytes, uint32_t max_occ, kmi_read_seeds *rows_dev, size_t cap_reads,
+                                    uint32_t *occ_dev, uint64_t *offsets_dev, size_t cap_kmers, uint64_t *values_dev, size_t cap_hits,
+                                    uint64_t *n_reads, uint64_t *n_kmers, uint64_t *n_hits) {
+  return seed_reads_entry(idx, bytes_dev, n_bytes, true, max_occ, rows_dev, cap_reads, occ_dev, offsets_dev, cap_kmers, values_dev, cap_hits, n_reads,
+                          n_kmers, n_hits);
+}
+kmi_status kmi_index_seed_reads_host(kmi_index *idx, const uint8_t *bytes, size_t n_bytes, uint32_t max_occ, kmi_read_seeds *rows, size_t cap_reads,
+                                     uint32_t *occ, uint64_t *offsets, size_t cap_kmers, uint64_t *values, size_t cap_hits, uint64_t *n_reads,
+                                     uint64_t *n_kmers, uint64_t *n_hits) {
+  return seed_reads_entry(idx, bytes, n_bytes, false, max_occ, rows, cap_reads, occ, offsets, cap_kmers, values, cap_hits, n_reads, n_kmers, n_hits);
 }
 
 // ---- count spectrum and count filter (kmi_spectrum.h)

@@ -66,6 +66,9 @@ enum WsSlot {
   WS_LOOKUP_RECS,     // positional lookup / read profile (kmi_lookup.h): (key words, tag) records of the queries or of a batch's k-mers
   WS_LOOKUP_CNT,      // ... the looked-up count of every k-mer of a batch, in file order
   WS_SPECTRUM,        // count spectrum / count filter (kmi_spectrum.h): the call's device scalars, then the survivors of every fine bucket
+  WS_LOCATE_POS,      // locate / seed_reads (kmi_locate.h): entry positions of every fine bucket grouped by key, one u32 per index entry
+  WS_LOCATE_SCAN,     // ... tile sums of the device-wide scans
+  WS_LOCATE_OFF,      // ... offsets[] of a batch's windows, or of the host form's queries
   WS_NUM_SLOTS
 };
 
@@ -88,8 +91,8 @@ enum FlagWord : uint32_t {
   FLAG_SK_LEVEL0 = 16,      // sk_reduce_kernel: buckets that ended at level 0 .. 8 (9 words); sk_back_end clears and reads (the next build's hint)
   FLAG_SK_LEVEL_END = 34,   // (words 25 .. 33 are cleared with the votes and unused)
   FLAG_SK_ROOM = 34,        // sk_scatter_fine_slack_lines_kernel: a fine bucket outgrew its room; sk_zero_kernel clears; sk_back_end reads
-  FLAG_LOOKUP_NPASS = 36,   // bucket_lookup_kernel: the largest pass count of the call's buckets; lookup clears and reads
-  FLAG_LOOKUP_OVER = 37,    // bucket_lookup_kernel: a bucket went over the pass limit; lookup clears and reads
+  FLAG_LOOKUP_NPASS = 36,   // bucket_lookup_kernel, bucket_locate_*_kernel: the largest pass count of the call's buckets; lookup clears and reads
+  FLAG_LOOKUP_OVER = 37,    // bucket_lookup_kernel, bucket_locate_*_kernel: a bucket went over the pass limit; lookup clears and reads
   FLAG_REDUCE_QUEUE = 40,   // sk_reduce_kernel: the next fine bucket to hand out (41 .. 47 spare, cleared with it); sk_back_end clears
   FLAG_REDUCE_QUEUE_END = 48,
   FLAG_CLOCKS = 48,         // timing builds (KMI_FR_TIMING, KMI_SK_TIMING): 8 64-bit wave clocks; the reports read and clear them
@@ -125,14 +128,16 @@ enum TotalWord : uint32_t {
   TOT_SK_KMERS = 6,        // k-mers of a super-k-mer build: sk_front / fasta_runs / sk_recv_hist add; sk_zero_kernel or a fill clears; the front ends read
   TOT_UPDATED = 7,          // update kernels: entries changed; update clears and reads
   TOT_BATCH_END = 8,        // fastq_batch_end_kernel writes; fastq_batch_end reads
+  TOT_LOCATE_HITS = 9,      // scan_tile_bases_kernel (kmi_locate.h): the listed hits up to the end of the call's / batch's queries; locate_read_total reads
   TOT_FRONT = 12,           // sk_front_verify_kernel: lines, runs, items (3 words); sk_front_fast reads
   TOT_COARSE = 16,          // fine_totals_kernel: [256] coarse totals of the fine-offset scan (launch_fine_offsets)
   TOT_NUM_WORDS = 16 + 256
 };
-// one owner per total word: the named words in ascending order with nothing between two of them unaccounted for (9 .. 11 and 15 are free)
+// one owner per total word: the named words in ascending order with nothing between two of them unaccounted for (10, 11 and 15 are free)
 static_assert(TOT_FA_VALID + 1 == TOT_SCAN_WORDS && TOT_SCAN_WORDS == TOT_ENTRIES && TOT_ENTRIES + 1 == TOT_RESULTS &&
               TOT_RESULTS + 1 == TOT_SK_KMERS && TOT_SK_KMERS + 1 == TOT_UPDATED && TOT_UPDATED + 1 == TOT_BATCH_END &&
-              TOT_BATCH_END < TOT_FRONT && TOT_FRONT + 3 <= TOT_COARSE && TOT_COARSE + 256 == TOT_NUM_WORDS, "one owner per total word");
+              TOT_BATCH_END + 1 == TOT_LOCATE_HITS && TOT_LOCATE_HITS < TOT_FRONT && TOT_FRONT + 3 <= TOT_COARSE && TOT_COARSE + 256 == TOT_NUM_WORDS,
+              "one owner per total word");
 // h_totals: words 0 .. 15 mirror d_totals under the TotalWord names (read_totals, fasta_scan, read_total copy word for word);
 // the words below are the host's own
 enum HostWord : uint32_t {
@@ -218,9 +223,9 @@ struct kmi_ctx {
   int sk_dbg = 0;                // KMI_SK_DBG=7 (test knob): the super-k-mer front end reports a capacity as exceeded
   bool fa_part_set = false;      // kmi_ctx_set_fasta_partition
   kmi_fasta_partition fa_part{};
-  uint32_t lookup_cap = 0;       // home slots of bucket_lookup_kernel's table (KMI_LOOKUP_CAP: tests reach the multi-pass code with a small index); 0: the table's own
+  uint32_t lookup_cap = 0;       // home slots of the tables of bucket_lookup_kernel, bucket_locate_*_kernel and the set operations (KMI_LOOKUP_CAP: tests reach the multi-pass code with a small index); 0: the table's own
   size_t profile_batch = (size_t)256 << 20;   // input bytes of a batch of kmi_index_profile_reads_* (KMI_PROFILE_BATCH)
-  uint64_t lookup_npass = 0;     // the largest pass count a bucket used in the last lookup / profile (kmi_ctx_debug_counter 8)
+  uint64_t lookup_npass = 0;     // the largest pass count a bucket used in the last lookup / profile / locate / seed_reads (kmi_ctx_debug_counter 8)
   uint64_t retain_fullest = 0;   // entries of the fullest bucket the last kmi_index_retain_counts met (kmi_ctx_debug_counter 9)
   uint64_t setops_npass = 0;     // the largest pass count a bucket used in the last kmi_index_compare / kmi_index_combine (kmi_ctx_debug_counter 10)
   int fa_left_carry = -1;        // de Bruijn tuples of a FASTA block (kmi_dbg_build_fasta_range_dist_host): the raw byte of the sequence
