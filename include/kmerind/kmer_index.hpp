@@ -701,20 +701,31 @@ class Index {
   }
 
   // ---- queries in the caller's order (no counterpart in the reference: count() / find() answer once per distinct key, unordered).
-  // Count indexes on one rank. lookup: out[i] = the count stored for query[i]'s transformed key, 0 when absent.
+  // With size() > 1 (or KMI_FORCE_DIST) all four are collective: every rank calls with ITS queries, or with the same file name, of
+  // which it takes its own record-aligned share (my_fastq_share, cut the way kmi_fastq_partition_dev cuts a buffer between ranks),
+  // and gets the answers for its own queries / reads, in its own order, from the entries of all ranks.
+  // Count indexes. lookup: out[i] = the count stored for query[i]'s transformed key, 0 when absent.
   std::vector<uint32_t> lookup(std::vector<KmerType> const &query) const {
     static_assert(MapType::index_kind == KMI_INDEX_COUNT, "lookup() is a member of the count index");
-    if (comm.size() > 1) throw std::invalid_argument("lookup() answers from one rank's entries: size() > 1 is not supported");
     std::vector<uint32_t> out(query.size());
-    ::kmerind::check(ctx, kmi_index_lookup_host(idx, detail::words_of(query), query.size(), out.data()));
+    if (over_ranks("lookup")) ::kmerind::check(ctx, kmi_index_lookup_dist_host(idx, rccl, detail::words_of(query), query.size(), out.data()));
+    else ::kmerind::check(ctx, kmi_index_lookup_host(idx, detail::words_of(query), query.size(), out.data()));
     return out;
   }
   // profile_reads: one kmi_read_profile row per record of a FASTQ file, in file order -- how many of the read's k-mers the index
   // holds, how many of them at least `solid` times, their lowest / highest / summed count. The file is read as build_posix reads it.
   std::vector<kmi_read_profile> profile_reads(const std::string &filename, uint32_t solid = 2) const {
     static_assert(MapType::index_kind == KMI_INDEX_COUNT, "profile_reads() is a member of the count index");
-    if (comm.size() > 1) throw std::invalid_argument("profile_reads() answers from one rank's entries: size() > 1 is not supported");
     if (detail::format_of(filename) != KMI_FMT_FASTQ) throw std::invalid_argument("profile_reads() reads FASTQ files");
+    if (over_ranks("profile_reads")) {   // the sizing call, then the filling call: both collective, on every rank
+      const std::vector<uint8_t> mine = my_fastq_share(filename);
+      uint64_t n = 0;
+      const kmi_status st = kmi_index_profile_reads_dist_host(idx, rccl, mine.data(), mine.size(), solid, nullptr, 0, &n);
+      if (!(st == KMI_ERR_OVERFLOW && n > 0)) ::kmerind::check(ctx, st);
+      std::vector<kmi_read_profile> rows((size_t)n);
+      ::kmerind::check(ctx, kmi_index_profile_reads_dist_host(idx, rccl, mine.data(), mine.size(), solid, n ? rows.data() : nullptr, rows.size(), &n));
+      return rows;
+    }
     const std::vector<uint8_t> bytes = detail::read_whole_file(filename);
     size_t cap = 2;   // every record but the last ends four lines
     for (uint8_t c : bytes) cap += (c == '\n');
@@ -730,21 +741,25 @@ class Index {
     out.resize((size_t)n);
     return out;
   }
-  // Position indexes on one rank. locate: occ[i] = entries under query[i]'s transformed key; values[offsets[i] .. offsets[i + 1]) =
+  // Position indexes. locate: occ[i] = entries under query[i]'s transformed key; values[offsets[i] .. offsets[i + 1]) =
   // their values when occ[i] <= max_occ, nothing otherwise (a key is listed whole or not at all); one answer per query, in query
   // order. Under the canonical strand model a hit does not tell the orientation of the reference occurrence.
   struct Located { std::vector<uint32_t> occ; std::vector<uint64_t> offsets; std::vector<ValueType> values; };
   Located locate(std::vector<KmerType> const &query, uint32_t max_occ = KMI_LOCATE_ALL) const {
     static_assert(MapType::index_kind != KMI_INDEX_COUNT, "locate() is a member of the position indexes");
-    if (comm.size() > 1) throw std::invalid_argument("locate() answers from one rank's entries: size() > 1 is not supported");
     constexpr unsigned vw = detail::stored_words<MapType, ValueType>();
+    const bool ranks = over_ranks("locate");
     Located out;
     out.occ.resize(query.size());
     out.offsets.resize(query.size() + 1);
     uint64_t n = 0;
-    ::kmerind::check(ctx, kmi_index_locate_host(idx, detail::words_of(query), query.size(), max_occ, out.occ.data(), out.offsets.data(), nullptr, 0, &n));
+    auto call = [&](uint64_t *values, size_t capacity) {
+      return ranks ? kmi_index_locate_dist_host(idx, rccl, detail::words_of(query), query.size(), max_occ, out.occ.data(), out.offsets.data(), values, capacity, &n)
+                   : kmi_index_locate_host(idx, detail::words_of(query), query.size(), max_occ, out.occ.data(), out.offsets.data(), values, capacity, &n);
+    };
+    ::kmerind::check(ctx, call(nullptr, 0));
     std::vector<uint64_t> words((size_t)n * vw);
-    if (n) ::kmerind::check(ctx, kmi_index_locate_host(idx, detail::words_of(query), query.size(), max_occ, out.occ.data(), out.offsets.data(), words.data(), (size_t)n, &n));
+    if (n || ranks) ::kmerind::check(ctx, call(n ? words.data() : nullptr, (size_t)n));   // (over ranks the filling call is every rank's)
     out.values.resize((size_t)n);
     for (uint64_t i = 0; i < n; ++i) out.values[i] = detail::stored_value<MapType, ValueType>(&words[i * vw]);
     return out;
@@ -755,20 +770,23 @@ class Index {
   struct Seeds { std::vector<kmi_read_seeds> reads; std::vector<uint32_t> occ; std::vector<uint64_t> offsets; std::vector<ValueType> values; };
   Seeds seed_reads(const std::string &fastq, uint32_t max_occ = KMI_LOCATE_ALL) const {
     static_assert(MapType::index_kind != KMI_INDEX_COUNT, "seed_reads() is a member of the position indexes");
-    if (comm.size() > 1) throw std::invalid_argument("seed_reads() answers from one rank's entries: size() > 1 is not supported");
     if (detail::format_of(fastq) != KMI_FMT_FASTQ) throw std::invalid_argument("seed_reads() reads FASTQ files");
     constexpr unsigned vw = detail::stored_words<MapType, ValueType>();
-    const std::vector<uint8_t> bytes = detail::read_whole_file(fastq);
+    const bool ranks = over_ranks("seed_reads");
+    const std::vector<uint8_t> bytes = ranks ? my_fastq_share(fastq) : detail::read_whole_file(fastq);
     uint64_t nr = 0, nk = 0, nh = 0;
-    ::kmerind::check(ctx, kmi_index_seed_reads_host(idx, bytes.data(), bytes.size(), max_occ, nullptr, 0, nullptr, nullptr, 0, nullptr, 0, &nr, &nk, &nh));
+    auto call = [&](kmi_read_seeds *rows, size_t cr, uint32_t *occ, uint64_t *offsets, size_t ck, uint64_t *values, size_t ch) {
+      return ranks ? kmi_index_seed_reads_dist_host(idx, rccl, bytes.data(), bytes.size(), max_occ, rows, cr, occ, offsets, ck, values, ch, &nr, &nk, &nh)
+                   : kmi_index_seed_reads_host(idx, bytes.data(), bytes.size(), max_occ, rows, cr, occ, offsets, ck, values, ch, &nr, &nk, &nh);
+    };
+    ::kmerind::check(ctx, call(nullptr, 0, nullptr, nullptr, 0, nullptr, 0));
     Seeds out;
     out.reads.resize((size_t)nr);
     out.occ.resize((size_t)nk);
     out.offsets.resize((size_t)nk + 1);
     std::vector<uint64_t> words((size_t)nh * vw);
-    ::kmerind::check(ctx, kmi_index_seed_reads_host(idx, bytes.data(), bytes.size(), max_occ, nr ? out.reads.data() : nullptr, (size_t)nr,
-                                                    nk ? out.occ.data() : nullptr, out.offsets.data(), (size_t)nk, nh ? words.data() : nullptr, (size_t)nh,
-                                                    &nr, &nk, &nh));
+    ::kmerind::check(ctx, call(nr ? out.reads.data() : nullptr, (size_t)nr, nk ? out.occ.data() : nullptr, out.offsets.data(), (size_t)nk,
+                               nh ? words.data() : nullptr, (size_t)nh));
     out.values.resize((size_t)nh);
     for (uint64_t i = 0; i < nh; ++i) out.values[i] = detail::stored_value<MapType, ValueType>(&words[i * vw]);
     return out;
@@ -955,6 +973,25 @@ class Index {
     uint64_t n = 0;
     ::kmerind::check(ctx, kmi_index_erase_host(idx, detail::words_of(keys), keys.size(), &n));
     ::kmerind::check(ctx, kmi_index_insert_pairs_host(idx, rec.data(), keys.size()));
+  }
+  // the queries in the caller's order: the collective form when the index is held over ranks (or KMI_FORCE_DIST made a communicator)
+  bool over_ranks(const char *what) const {
+    if (comm.size() == 1 && !rccl) return false;
+    need_rccl(what);
+    return true;
+  }
+  // this rank's record-aligned share of a FASTQ file: range comm.rank() of the cuts kmi_fastq_partition_dev gives for comm.size() parts
+  std::vector<uint8_t> my_fastq_share(const std::string &filename) const {
+    std::vector<uint8_t> bytes = detail::read_whole_file(filename);
+    if (comm.size() == 1 || bytes.empty()) return bytes;
+    void *d = nullptr;
+    ::kmerind::check(ctx, kmi_device_alloc(ctx, bytes.size() + 64, &d));
+    std::vector<uint64_t> cuts((size_t)comm.size() + 1, 0);
+    kmi_status st = kmi_copy_to_device(ctx, d, bytes.data(), bytes.size());
+    if (st == KMI_OK) st = kmi_fastq_partition_dev(ctx, (const uint8_t *)d, bytes.size(), (uint32_t)comm.size(), cuts.data());
+    (void)kmi_device_free(ctx, d);
+    ::kmerind::check(ctx, st);
+    return std::vector<uint8_t>(bytes.begin() + (long)cuts[(size_t)comm.rank()], bytes.begin() + (long)cuts[(size_t)comm.rank() + 1]);
   }
   void need_rccl(const char *what) const {
     if (!rccl) throw std::invalid_argument(std::string(what) + " with size() > 1 needs the RCCL communicator (comm.unique_id)");

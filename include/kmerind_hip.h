@@ -446,8 +446,8 @@ kmi_status kmi_index_update_pairs_dev(kmi_index *idx, const uint64_t *records_de
  * key, in no particular order, and it has no per-read query at all)
  * Count indexes only (KMI_INDEX_COUNT); a position index gives KMI_ERR_INVALID. Every k-mer shape a count index takes (one to four
  * words; 2-, 3- and 4-bit alphabets), both layouts (placement hash, and the minimizer layout a super-k-mer build leaves), dense and
- * sparse indexes alike. The index is not changed (a sparse index stays sparse); an empty index answers 0 everywhere. One rank's
- * entries only: an index spread over ranks answers for this rank's share.
+ * sparse indexes alike. The index is not changed (a sparse index stays sparse); an empty index answers 0 everywhere. These
+ * two answer from this rank's entries; kmi_index_lookup_dist_* / kmi_index_profile_reads_dist_* below answer from all ranks'.
  *
  * lookup: counts[i] = the count stored for InputTransform(queries[i]) (the transform find() applies), 0 when it is not in the
  * index. One answer per query, in query order; a key asked twice is answered twice. nq == 0 is fine.
@@ -491,7 +491,7 @@ kmi_status kmi_index_profile_reads_host(kmi_index *idx, const uint8_t *bytes, si
  * reference: its find() returns the (key, value) pairs of the distinct queried keys in no particular order, and it has no cap on
  * repetitive keys and no per-read query)
  * Position and position + quality indexes only (KMI_INDEX_POSITION, KMI_INDEX_POSQUAL); a count index gives KMI_ERR_INVALID. Every
- * key shape these indexes take (one to four words). One rank's entries only, as for lookup. The index is never changed.
+ * key shape these indexes take (one to four words). This rank's entries, as for lookup (the _dist_ forms below: all ranks'). The index is never changed.
  * Strand. Under the canonical strand model a hit does not tell the orientation of the reference occurrence relative to the query:
  * the index stores the canonical k-mer and the position, not which strand of the reference spelled it.
  *
@@ -544,6 +544,55 @@ kmi_status kmi_index_seed_reads_host(kmi_index *idx, const uint8_t *bytes, size_
                                      uint32_t *occ, uint64_t *offsets /* cap_kmers + 1 */, size_t cap_kmers,
                                      uint64_t *values, size_t cap_hits,
                                      uint64_t *n_reads, uint64_t *n_kmers, uint64_t *n_hits);
+
+/* ---- the queries in the caller's order against an index held over ranks (collective)
+ * lookup, profile_reads, locate and seed_reads with the arguments and results of the one-rank calls above, answered from the entries
+ * of ALL ranks of `comm`. Every rank of the communicator makes the call, each with its own queries or its own record-aligned FASTQ
+ * share; nq == 0 or n_bytes == 0 on some or all ranks is fine. A rank's answers are for its own queries, in its own order. A key
+ * lives wholly on the rank that owns it, so occ is the true multiplicity over the whole index and "listed whole or not at all"
+ * keeps its meaning; first_kmer, offsets and seq_offset are relative to the rank's own buffer, as on one rank.
+ *  - One rank. With a communicator of one rank (and no KMI_FORCE_DIST) the call is the one-rank call.
+ *  - Owners. The queries travel to the rank that owns the key under the rule the index was built with: the minimizer-bucket owner
+ *    of a build through exchanged super-k-mers (kmi_route_owner_dev), KeyToRank (kmi_route_dev) else. Only the key words travel;
+ *    where a query sits in the caller's array stays on its rank. The owner answers everything it received in one pass of the
+ *    one-rank code; count / occ come back as 4 bytes per key, the listed values of locate as one message per source.
+ *  - Refusals. A wrong index kind, max_occ == 0, solid_threshold == 0, a null buffer, a communicator of another context and an
+ *    index whose owner ranks (kmi_index_owner_ranks, when not 1) are not the communicator's size give KMI_ERR_INVALID on that rank
+ *    before anything collective.
+ *  - Errors. A rank-local verdict is all-reduced before the first exchange of the call -- of every batch round for the reads forms
+ *    -- and again behind the owners' pass: a parse error, the 65535-byte record limit and a bucket past the pass limit end the call
+ *    on every rank; the failing rank returns its own error, the others KMI_ERR_PEER, and no output is promised.
+ *  - Capacities. A short capacity is no such error and changes nothing that is sent or received: that rank takes part in every
+ *    round, writes nothing past its capacity and returns KMI_ERR_OVERFLOW with exact totals (for locate: with occ and offsets in
+ *    full), its peers return KMI_OK with full answers. The sizing call (all output buffers NULL, zero capacities) is collective too
+ *    and runs the same exchanges; the values travel when any rank of the call asked for them.
+ *  - Batches. The reads forms work in record-aligned batches of KMI_PROFILE_BATCH bytes, one round per batch; a rank that has run
+ *    out of input takes part with zero queries until every rank has. The results do not depend on the batch size.
+ * kmi_ctx_debug_counter 8 tells the largest pass count of the buckets this rank answered as an owner; 11 the number of output hits
+ * a workgroup of the copy that brings the returned values into query order owns; 12 the keys this rank answered as their owner
+ * in the last of these calls. */
+kmi_status kmi_index_lookup_dist_dev (kmi_index *idx, kmi_comm *comm, const uint64_t *queries_dev, size_t nq, uint32_t *counts_dev);
+kmi_status kmi_index_lookup_dist_host(kmi_index *idx, kmi_comm *comm, const uint64_t *queries,     size_t nq, uint32_t *counts);
+kmi_status kmi_index_profile_reads_dist_dev (kmi_index *idx, kmi_comm *comm, const uint8_t *bytes_dev, size_t n_bytes, uint32_t solid_threshold,
+                                             kmi_read_profile *out_dev, size_t capacity, uint64_t *n_reads);
+kmi_status kmi_index_profile_reads_dist_host(kmi_index *idx, kmi_comm *comm, const uint8_t *bytes, size_t n_bytes, uint32_t solid_threshold,
+                                             kmi_read_profile *out, size_t capacity, uint64_t *n_reads);
+kmi_status kmi_index_locate_dist_dev (kmi_index *idx, kmi_comm *comm, const uint64_t *queries_dev, size_t nq, uint32_t max_occ,
+                                      uint32_t *occ_dev /* nq */, uint64_t *offsets_dev /* nq + 1 */,
+                                      uint64_t *values_dev, size_t capacity /* hits */, uint64_t *n_hits);
+kmi_status kmi_index_locate_dist_host(kmi_index *idx, kmi_comm *comm, const uint64_t *queries, size_t nq, uint32_t max_occ,
+                                      uint32_t *occ /* nq */, uint64_t *offsets /* nq + 1 */,
+                                      uint64_t *values, size_t capacity /* hits */, uint64_t *n_hits);
+kmi_status kmi_index_seed_reads_dist_dev (kmi_index *idx, kmi_comm *comm, const uint8_t *bytes_dev, size_t n_bytes, uint32_t max_occ,
+                                          kmi_read_seeds *rows_dev, size_t cap_reads,
+                                          uint32_t *occ_dev, uint64_t *offsets_dev /* cap_kmers + 1 */, size_t cap_kmers,
+                                          uint64_t *values_dev, size_t cap_hits,
+                                          uint64_t *n_reads, uint64_t *n_kmers, uint64_t *n_hits);
+kmi_status kmi_index_seed_reads_dist_host(kmi_index *idx, kmi_comm *comm, const uint8_t *bytes, size_t n_bytes, uint32_t max_occ,
+                                          kmi_read_seeds *rows, size_t cap_reads,
+                                          uint32_t *occ, uint64_t *offsets /* cap_kmers + 1 */, size_t cap_kmers,
+                                          uint64_t *values, size_t cap_hits,
+                                          uint64_t *n_reads, uint64_t *n_kmers, uint64_t *n_hits);
 
 /* ---- the count spectrum, and the filter by count (no counterpart in the reference beyond to_vector() plus a host loop, the way
  * its erase_if(pred) works)

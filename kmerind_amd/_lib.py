@@ -170,6 +170,14 @@ SIGNATURES = {
     "kmi_index_locate_host": (C.c_int, [_P, _P, _sz, _u32, _P, _P, _P, _sz, C.POINTER(_u64)]),
     "kmi_index_seed_reads_dev": (C.c_int, [_P, _P, _sz, _u32, _P, _sz, _P, _P, _sz, _P, _sz, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
     "kmi_index_seed_reads_host": (C.c_int, [_P, _P, _sz, _u32, _P, _sz, _P, _P, _sz, _P, _sz, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "kmi_index_lookup_dist_dev": (C.c_int, [_P, _P, _P, _sz, _P]),
+    "kmi_index_lookup_dist_host": (C.c_int, [_P, _P, _P, _sz, _P]),
+    "kmi_index_profile_reads_dist_dev": (C.c_int, [_P, _P, _P, _sz, _u32, _P, _sz, C.POINTER(_u64)]),
+    "kmi_index_profile_reads_dist_host": (C.c_int, [_P, _P, _P, _sz, _u32, _P, _sz, C.POINTER(_u64)]),
+    "kmi_index_locate_dist_dev": (C.c_int, [_P, _P, _P, _sz, _u32, _P, _P, _P, _sz, C.POINTER(_u64)]),
+    "kmi_index_locate_dist_host": (C.c_int, [_P, _P, _P, _sz, _u32, _P, _P, _P, _sz, C.POINTER(_u64)]),
+    "kmi_index_seed_reads_dist_dev": (C.c_int, [_P, _P, _P, _sz, _u32, _P, _sz, _P, _P, _sz, _P, _sz, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
+    "kmi_index_seed_reads_dist_host": (C.c_int, [_P, _P, _P, _sz, _u32, _P, _sz, _P, _P, _sz, _P, _sz, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
     "kmi_index_spectrum_dev": (C.c_int, [_P, _u32, _P, C.POINTER(SpectrumTotals)]),
     "kmi_index_spectrum_host": (C.c_int, [_P, _u32, _P, C.POINTER(SpectrumTotals)]),
     "kmi_index_spectrum_dist_host": (C.c_int, [_P, _P, _u32, _P, C.POINTER(SpectrumTotals)]),

@@ -331,23 +331,41 @@ class CountIndex:
         return n.value
 
     # ---- queries in the caller's order (no reference counterpart; a position index refuses them)
-    def lookup(self, q):
-        """counts[i] = the count stored for the transformed q[i], 0 when absent: one answer per query, in query order"""
+    def _over(self, comm):
+        """the leading arguments of a query: the index, and the communicator of its collective form (anything with a kmi_comm
+        handle `h`)"""
+        return (self.h,) if comm is None else (self.h, comm.h)
+
+    def lookup(self, q, comm=None):
+        """counts[i] = the count stored for the transformed q[i], 0 when absent: one answer per query, in query order. With a
+        communicator the answers come from the entries of all ranks: collective, every rank with its own queries."""
         q = _u64(q, self.n_words)
         out = np.zeros(q.shape[0], dtype=np.uint32)
-        self.ctx.check(lib.kmi_index_lookup_host(self.h, q.ctypes.data_as(C.c_void_p), q.shape[0], out.ctypes.data_as(C.c_void_p)))
+        fn = lib.kmi_index_lookup_host if comm is None else lib.kmi_index_lookup_dist_host
+        self.ctx.check(fn(*self._over(comm), q.ctypes.data_as(C.c_void_p), q.shape[0], out.ctypes.data_as(C.c_void_p)))
         return out
 
-    def lookup_device(self, q_dptr, n, out_dptr):
+    def lookup_device(self, q_dptr, n, out_dptr, comm=None):
         """q_dptr: n k-mers of n_words u64 on the device; out_dptr: n u32 counts"""
-        self.ctx.check(lib.kmi_index_lookup_dev(self.h, C.c_void_p(q_dptr), n, C.c_void_p(out_dptr)))
+        fn = lib.kmi_index_lookup_dev if comm is None else lib.kmi_index_lookup_dist_dev
+        self.ctx.check(fn(*self._over(comm), C.c_void_p(q_dptr), n, C.c_void_p(out_dptr)))
 
-    def profile_reads(self, data, solid=2):
+    def profile_reads(self, data, solid=2, comm=None):
         """one row (READ_PROFILE_DTYPE) per FASTQ record of `data`, in file order: how many of the read's k-mers the index
-        holds, how many of them at least `solid` times, and the lowest / highest / summed count"""
+        holds, how many of them at least `solid` times, and the lowest / highest / summed count. With a communicator the counts
+        come from the entries of all ranks: collective, every rank with its own record-aligned share (a sizing call, then the
+        filling call, on every rank)."""
         buf = np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else \
             np.ascontiguousarray(data, dtype=np.uint8)
         n = C.c_uint64()
+        if comm is not None:
+            head = (self.h, comm.h, buf.ctypes.data_as(C.c_void_p) if buf.size else None, buf.size, solid)
+            st = lib.kmi_index_profile_reads_dist_host(*head, None, 0, C.byref(n))
+            if not (st == L.ERR_OVERFLOW and n.value > 0):   # (rows and no room for them: what the sizing call is for)
+                self.ctx.check(st)
+            out = np.zeros(n.value, dtype=READ_PROFILE_DTYPE)
+            self.ctx.check(lib.kmi_index_profile_reads_dist_host(*head, out.ctypes.data_as(C.c_void_p) if n.value else None, n.value, C.byref(n)))
+            return out
         cap = int(np.count_nonzero((buf == 10) | (buf == 13))) // 4 + 2   # (every record but the last ends four lines)
         while True:
             out = np.zeros(cap, dtype=READ_PROFILE_DTYPE)
@@ -359,10 +377,12 @@ class CountIndex:
             self.ctx.check(st)
             return out[:n.value].copy()
 
-    def profile_reads_device(self, dptr, nbytes, out_dptr, capacity, solid=2):
+    def profile_reads_device(self, dptr, nbytes, out_dptr, capacity, solid=2, comm=None):
         """dptr: FASTQ bytes on the device; out_dptr: room for `capacity` rows of 40 bytes -> number of records"""
         n = C.c_uint64()
-        st = lib.kmi_index_profile_reads_dev(self.h, C.c_void_p(dptr), nbytes, solid, C.c_void_p(out_dptr), capacity, C.byref(n))
+        fn = lib.kmi_index_profile_reads_dev if comm is None else lib.kmi_index_profile_reads_dist_dev
+        st = fn(*self._over(comm), C.c_void_p(dptr) if dptr else None, nbytes, solid, C.c_void_p(out_dptr) if out_dptr else None, capacity,
+                C.byref(n))
         if st != L.OK:
             err = L.KmiError(st, (lib.kmi_last_error(self.ctx.h) or b"").decode())
             err.n_reads = n.value
@@ -480,43 +500,49 @@ class PositionIndex(CountIndex):
             setattr(err, name, v)
         raise err
 
-    def locate(self, q, max_occ=None):
+    def locate(self, q, max_occ=None, comm=None):
         """(occ, offsets, values): occ[i] = entries under the transformed q[i]; values[offsets[i]:offsets[i + 1]] = their value
-        rows (shape (n_hits, value_words)) when occ[i] <= max_occ, nothing otherwise. One answer per query, in query order."""
+        rows (shape (n_hits, value_words)) when occ[i] <= max_occ, nothing otherwise. One answer per query, in query order. With a
+        communicator the answers come from the entries of all ranks: collective, every rank with its own queries (a sizing call,
+        then the filling call, on every rank)."""
         q = _u64(q, self.n_words)
         nq = q.shape[0]
         max_occ = L.LOCATE_ALL if max_occ is None else int(max_occ)
         occ = np.zeros(nq, dtype=np.uint32)
         offsets = np.zeros(nq + 1, dtype=np.uint64)
         n = C.c_uint64()
-        args = (self.h, q.ctypes.data_as(C.c_void_p), nq, max_occ, occ.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p))
-        self.ctx.check(lib.kmi_index_locate_host(*args, None, 0, C.byref(n)))   # the sizing call
+        fn = lib.kmi_index_locate_host if comm is None else lib.kmi_index_locate_dist_host
+        args = (*self._over(comm), q.ctypes.data_as(C.c_void_p), nq, max_occ, occ.ctypes.data_as(C.c_void_p), offsets.ctypes.data_as(C.c_void_p))
+        self.ctx.check(fn(*args, None, 0, C.byref(n)))   # the sizing call
         values = np.zeros((n.value, self.value_words), dtype=np.uint64)
-        if n.value:
-            self.ctx.check(lib.kmi_index_locate_host(*args, values.ctypes.data_as(C.c_void_p), n.value, C.byref(n)))
+        if n.value or comm is not None:   # (over ranks the filling call is every rank's, also a rank's without a hit)
+            self.ctx.check(fn(*args, values.ctypes.data_as(C.c_void_p) if n.value else None, n.value, C.byref(n)))
         return occ, offsets, values
 
-    def locate_device(self, q_dptr, n, occ_dptr, offsets_dptr, values_dptr=0, capacity=0, max_occ=None):
+    def locate_device(self, q_dptr, n, occ_dptr, offsets_dptr, values_dptr=0, capacity=0, max_occ=None, comm=None):
         """q_dptr: n k-mers on the device; occ_dptr: n u32; offsets_dptr: n + 1 u64; values_dptr: room for `capacity` hits of
         value_words u64 (0 with capacity 0: the sizing call) -> number of listed hits"""
         max_occ = L.LOCATE_ALL if max_occ is None else int(max_occ)
         hits = C.c_uint64()
-        st = lib.kmi_index_locate_dev(self.h, C.c_void_p(q_dptr), n, max_occ, C.c_void_p(occ_dptr), C.c_void_p(offsets_dptr),
-                                      C.c_void_p(values_dptr) if values_dptr else None, capacity, C.byref(hits))
+        fn = lib.kmi_index_locate_dev if comm is None else lib.kmi_index_locate_dist_dev
+        st = fn(*self._over(comm), C.c_void_p(q_dptr), n, max_occ, C.c_void_p(occ_dptr), C.c_void_p(offsets_dptr),
+                C.c_void_p(values_dptr) if values_dptr else None, capacity, C.byref(hits))
         if st != L.OK:
             self._raise(st, n_hits=hits.value)
         return hits.value
 
-    def seed_reads(self, data, max_occ=None):
+    def seed_reads(self, data, max_occ=None, comm=None):
         """(rows, occ, offsets, values): one row (READ_SEEDS_DTYPE) per FASTQ record of `data`, in file order; window j of read r
-        is query rows[r]['first_kmer'] + j of the locate() arrays over all windows of the buffer"""
+        is query rows[r]['first_kmer'] + j of the locate() arrays over all windows of the buffer. With a communicator the hits
+        come from the entries of all ranks: collective, every rank with its own record-aligned share."""
         buf = np.frombuffer(bytes(data), dtype=np.uint8) if isinstance(data, (bytes, bytearray)) else \
             np.ascontiguousarray(data, dtype=np.uint8)
         max_occ = L.LOCATE_ALL if max_occ is None else int(max_occ)
         nr, nk, nh = C.c_uint64(), C.c_uint64(), C.c_uint64()
         tail = (C.byref(nr), C.byref(nk), C.byref(nh))
-        head = (self.h, buf.ctypes.data_as(C.c_void_p), buf.size, max_occ)
-        self.ctx.check(lib.kmi_index_seed_reads_host(*head, None, 0, None, None, 0, None, 0, *tail))   # the sizing call
+        fn = lib.kmi_index_seed_reads_host if comm is None else lib.kmi_index_seed_reads_dist_host
+        head = (*self._over(comm), buf.ctypes.data_as(C.c_void_p) if buf.size else None, buf.size, max_occ)
+        self.ctx.check(fn(*head, None, 0, None, None, 0, None, 0, *tail))   # the sizing call
         rows = np.zeros(nr.value, dtype=READ_SEEDS_DTYPE)
         occ = np.zeros(nk.value, dtype=np.uint32)
         offsets = np.zeros(nk.value + 1, dtype=np.uint64)
@@ -524,12 +550,11 @@ class PositionIndex(CountIndex):
 
         def ptr(a):
             return a.ctypes.data_as(C.c_void_p) if a.size else None
-        self.ctx.check(lib.kmi_index_seed_reads_host(*head, ptr(rows), rows.size, ptr(occ), offsets.ctypes.data_as(C.c_void_p), occ.size,
-                                                     ptr(values), values.shape[0], *tail))
+        self.ctx.check(fn(*head, ptr(rows), rows.size, ptr(occ), offsets.ctypes.data_as(C.c_void_p), occ.size, ptr(values), values.shape[0], *tail))
         return rows, occ, offsets, values
 
     def seed_reads_device(self, dptr, nbytes, rows_dptr=0, cap_reads=0, occ_dptr=0, offsets_dptr=0, cap_kmers=0, values_dptr=0, cap_hits=0,
-                          max_occ=None):
+                          max_occ=None, comm=None):
         """dptr: FASTQ bytes on the device; rows_dptr: room for cap_reads rows of 32 bytes; occ_dptr: cap_kmers u32; offsets_dptr:
         cap_kmers + 1 u64; values_dptr: cap_hits hits of value_words u64 (all 0: the sizing call) -> (n_reads, n_kmers, n_hits)"""
         max_occ = L.LOCATE_ALL if max_occ is None else int(max_occ)
@@ -537,8 +562,9 @@ class PositionIndex(CountIndex):
 
         def ptr(p):
             return C.c_void_p(p) if p else None
-        st = lib.kmi_index_seed_reads_dev(self.h, C.c_void_p(dptr), nbytes, max_occ, ptr(rows_dptr), cap_reads, ptr(occ_dptr), ptr(offsets_dptr),
-                                          cap_kmers, ptr(values_dptr), cap_hits, C.byref(nr), C.byref(nk), C.byref(nh))
+        fn = lib.kmi_index_seed_reads_dev if comm is None else lib.kmi_index_seed_reads_dist_dev
+        st = fn(*self._over(comm), ptr(dptr), nbytes, max_occ, ptr(rows_dptr), cap_reads, ptr(occ_dptr), ptr(offsets_dptr), cap_kmers,
+                ptr(values_dptr), cap_hits, C.byref(nr), C.byref(nk), C.byref(nh))
         if st != L.OK:
             self._raise(st, n_reads=nr.value, n_kmers=nk.value, n_hits=nh.value)
         return nr.value, nk.value, nh.value

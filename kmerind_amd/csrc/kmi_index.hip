@@ -4292,6 +4292,8 @@ static kmi_status dist_state(kmi_index *idx, kmi_comm *comm, uint64_t *holders, 
   return KMI_OK;
 }
 
+#include "kmi_query_dist.h"
+
 // The count index over ranks through exchanged super-k-mer records, CHUNKED: the rank's share is cut into record-aligned chunks;
 // the records of chunk c travel on the communicator's stream while the front end of chunk c + 1 runs on the context's; the
 // counts of a chunk ride with the verdict ("this rank could not produce it": then every rank sends that chunk as k-mers to the
@@ -5383,6 +5385,139 @@ kmi_status kmi_index_seed_reads_host(kmi_index *idx, const uint8_t *bytes, size_
                                      uint32_t *occ, uint64_t *offsets, size_t cap_kmers, uint64_t *values, size_t cap_hits, uint64_t *n_reads,
                                      uint64_t *n_kmers, uint64_t *n_hits) {
   return seed_reads_entry(idx, bytes, n_bytes, false, max_occ, rows, cap_reads, occ, offsets, cap_kmers, values, cap_hits, n_reads, n_kmers, n_hits);
+}
+
+// ---- the same four over ranks (kmi_query_dist.h). Everything checked here is refused on this rank before anything collective.
+static kmi_status query_dist_check(kmi_index *idx, kmi_comm *comm, bool position, const char *what) {
+  KMI_TRY(dist_check(idx, comm));
+  kmi_ctx *ctx = idx->ctx;
+  if (position != (idx->val_words != 0))
+    return set_err(ctx, KMI_ERR_INVALID, position ? "%s() is a member of the position indexes" : "%s() is a member of the count index", what);
+  if (idx->owner_lp && (1u << idx->owner_lp) != (uint32_t)kmi::comm_size(comm))
+    return set_err(ctx, KMI_ERR_INVALID, "%s(): the index is distributed over another number of owner ranks than the communicator has", what);
+  return KMI_OK;
+}
+static bool query_dist_alone(kmi_index *idx, kmi_comm *comm) { return kmi::comm_size(comm) == 1 && !idx->ctx->force_dist; }
+
+kmi_status kmi_index_lookup_dist_dev(kmi_index *idx, kmi_comm *comm, const uint64_t *queries_dev, size_t nq, uint32_t *counts_dev) {
+  KMI_TRY(query_dist_check(idx, comm, false, "lookup"));
+  if (nq && (!queries_dev || !counts_dev)) return set_err(idx->ctx, KMI_ERR_INVALID, "null buffer");
+  if (query_dist_alone(idx, comm)) return kmi_index_lookup_dev(idx, queries_dev, nq, counts_dev);
+  return index_lookup_dist(idx, comm, queries_dev, nq, counts_dev);
+}
+
+kmi_status kmi_index_lookup_dist_host(kmi_index *idx, kmi_comm *comm, const uint64_t *queries, size_t nq, uint32_t *counts) {
+  KMI_TRY(query_dist_check(idx, comm, false, "lookup"));
+  kmi_ctx *ctx = idx->ctx;
+  if (nq && (!queries || !counts)) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
+  if (query_dist_alone(idx, comm)) return kmi_index_lookup_host(idx, queries, nq, counts);
+  void *dq = nullptr, *dc = nullptr;
+  const size_t q_bytes = nq * idx->shape.n_words * sizeof(uint64_t);
+  const kmi_status staged = [&]() -> kmi_status {
+    KMI_TRY(ws_get(ctx, WS_INPUT, q_bytes + 64, &dq));
+    KMI_TRY(ws_get(ctx, WS_OUTPUT, nq * sizeof(uint32_t) + 64, &dc));
+    if (nq) KMI_HIP(ctx, hipMemcpyAsync(dq, queries, q_bytes, hipMemcpyHostToDevice, ctx->stream));
+    return KMI_OK;
+  }();
+  if (staged != KMI_OK) { uint64_t more = 0, want = 0; return qd_agree(comm, staged, &more, &want); }   // (the peers are told in their first all-reduce)
+  KMI_TRY(index_lookup_dist(idx, comm, (const uint64_t *)dq, nq, (uint32_t *)dc));
+  if (nq) KMI_HIP(ctx, hipMemcpyAsync(counts, dc, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return KMI_OK;
+}
+
+static kmi_status profile_reads_dist_entry(kmi_index *idx, kmi_comm *comm, const uint8_t *bytes, size_t n_bytes, bool on_device, uint32_t solid_threshold,
+                                           kmi_read_profile *out, size_t capacity, uint64_t *n_reads) {
+  if (!n_reads) return KMI_ERR_INVALID;
+  *n_reads = 0;
+  KMI_TRY(query_dist_check(idx, comm, false, "profile_reads"));
+  kmi_ctx *ctx = idx->ctx;
+  if (idx->cfg.seq_format != KMI_FMT_FASTQ) return set_err(ctx, KMI_ERR_INVALID, "profile_reads() reads FASTQ");
+  if (solid_threshold == 0) return set_err(ctx, KMI_ERR_INVALID, "solid_threshold is at least 1");
+  if ((n_bytes && !bytes) || (!out && capacity)) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
+  if (query_dist_alone(idx, comm))
+    return on_device ? kmi_index_profile_reads_dev(idx, bytes, n_bytes, solid_threshold, out, capacity, n_reads)
+                     : kmi_index_profile_reads_host(idx, bytes, n_bytes, solid_threshold, out, capacity, n_reads);
+  return index_profile_reads_dist(idx, comm, bytes, n_bytes, on_device, solid_threshold, out, capacity, n_reads);
+}
+kmi_status kmi_index_profile_reads_dist_dev(kmi_index *idx, kmi_comm *comm, const uint8_t *bytes_dev, size_t n_bytes, uint32_t solid_threshold,
+                                            kmi_read_profile *out_dev, size_t capacity, uint64_t *n_reads) {
+  return profile_reads_dist_entry(idx, comm, bytes_dev, n_bytes, true, solid_threshold, out_dev, capacity, n_reads);
+}
+kmi_status kmi_index_profile_reads_dist_host(kmi_index *idx, kmi_comm *comm, const uint8_t *bytes, size_t n_bytes, uint32_t solid_threshold,
+                                             kmi_read_profile *out, size_t capacity, uint64_t *n_reads) {
+  return profile_reads_dist_entry(idx, comm, bytes, n_bytes, false, solid_threshold, out, capacity, n_reads);
+}
+
+kmi_status kmi_index_locate_dist_dev(kmi_index *idx, kmi_comm *comm, const uint64_t *queries_dev, size_t nq, uint32_t max_occ, uint32_t *occ_dev,
+                                     uint64_t *offsets_dev, uint64_t *values_dev, size_t capacity, uint64_t *n_hits) {
+  if (!n_hits) return KMI_ERR_INVALID;
+  *n_hits = 0;
+  KMI_TRY(query_dist_check(idx, comm, true, "locate"));
+  kmi_ctx *ctx = idx->ctx;
+  if (max_occ == 0) return set_err(ctx, KMI_ERR_INVALID, "max_occ is at least 1");
+  if (!offsets_dev || (nq && (!queries_dev || !occ_dev)) || (!values_dev && capacity)) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
+  if (query_dist_alone(idx, comm)) return kmi_index_locate_dev(idx, queries_dev, nq, max_occ, occ_dev, offsets_dev, values_dev, capacity, n_hits);
+  return index_locate_dist(idx, comm, queries_dev, nq, max_occ, occ_dev, offsets_dev, values_dev, capacity, n_hits);
+}
+
+kmi_status kmi_index_locate_dist_host(kmi_index *idx, kmi_comm *comm, const uint64_t *queries, size_t nq, uint32_t max_occ, uint32_t *occ,
+                                      uint64_t *offsets, uint64_t *values, size_t capacity, uint64_t *n_hits) {
+  if (!n_hits) return KMI_ERR_INVALID;
+  *n_hits = 0;
+  KMI_TRY(query_dist_check(idx, comm, true, "locate"));
+  kmi_ctx *ctx = idx->ctx;
+  if (max_occ == 0) return set_err(ctx, KMI_ERR_INVALID, "max_occ is at least 1");
+  if (!offsets || (nq && (!queries || !occ)) || (!values && capacity)) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
+  if (query_dist_alone(idx, comm)) return kmi_index_locate_host(idx, queries, nq, max_occ, occ, offsets, values, capacity, n_hits);
+  void *dq = nullptr, *dc = nullptr, *dof = nullptr, *dv = nullptr;
+  const size_t q_bytes = nq * idx->shape.n_words * sizeof(uint64_t), v_bytes = capacity * idx->val_words * sizeof(uint64_t);
+  const kmi_status staged = [&]() -> kmi_status {
+    KMI_TRY(ws_get(ctx, WS_INPUT, q_bytes + 64, &dq));
+    KMI_TRY(ws_get(ctx, WS_OUTPUT, nq * sizeof(uint32_t) + 64, &dc));
+    KMI_TRY(ws_get(ctx, WS_LOCATE_OFF, (nq + 1) * sizeof(uint64_t), &dof));
+    if (values) KMI_TRY(ws_get(ctx, WS_OUTPUT2, v_bytes + 64, &dv));
+    if (nq) KMI_HIP(ctx, hipMemcpyAsync(dq, queries, q_bytes, hipMemcpyHostToDevice, ctx->stream));
+    return KMI_OK;
+  }();
+  if (staged != KMI_OK) { uint64_t more = 0, want = 0; return qd_agree(comm, staged, &more, &want); }   // (the peers are told in their first all-reduce)
+  const kmi_status st = index_locate_dist(idx, comm, (const uint64_t *)dq, nq, max_occ, (uint32_t *)dc, (uint64_t *)dof, (uint64_t *)dv, capacity, n_hits);
+  if (st != KMI_OK && !(st == KMI_ERR_OVERFLOW && *n_hits > capacity)) return st;
+  // (occ and offsets are complete when only the capacity was short)
+  if (nq) KMI_HIP(ctx, hipMemcpyAsync(occ, dc, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  KMI_HIP(ctx, hipMemcpyAsync(offsets, dof, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (st == KMI_OK && values && *n_hits)
+    KMI_HIP(ctx, hipMemcpyAsync(values, dv, *n_hits * idx->val_words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return st;
+}
+
+static kmi_status seed_reads_dist_entry(kmi_index *idx, kmi_comm *comm, const uint8_t *bytes, size_t n_bytes, bool on_device, uint32_t max_occ,
+                                        kmi_read_seeds *rows, size_t cap_reads, uint32_t *occ, uint64_t *offsets, size_t cap_kmers, uint64_t *values,
+                                        size_t cap_hits, uint64_t *n_reads, uint64_t *n_kmers, uint64_t *n_hits) {
+  if (!n_reads || !n_kmers || !n_hits) return KMI_ERR_INVALID;
+  *n_reads = *n_kmers = *n_hits = 0;
+  KMI_TRY(query_dist_check(idx, comm, true, "seed_reads"));
+  kmi_ctx *ctx = idx->ctx;
+  if (max_occ == 0) return set_err(ctx, KMI_ERR_INVALID, "max_occ is at least 1");
+  if ((n_bytes && !bytes) || (!rows && cap_reads) || ((!occ || !offsets) && cap_kmers) || (!values && cap_hits))
+    return set_err(ctx, KMI_ERR_INVALID, "null buffer");
+  if (query_dist_alone(idx, comm))
+    return seed_reads_entry(idx, bytes, n_bytes, on_device, max_occ, rows, cap_reads, occ, offsets, cap_kmers, values, cap_hits, n_reads, n_kmers, n_hits);
+  return index_seed_reads_dist(idx, comm, bytes, n_bytes, on_device, max_occ, rows, cap_reads, occ, offsets, cap_kmers, values, cap_hits, n_reads,
+                               n_kmers, n_hits);
+}
+kmi_status kmi_index_seed_reads_dist_dev(kmi_index *idx, kmi_comm *comm, const uint8_t *bytes_dev, size_t n_bytes, uint32_t max_occ,
+                                         kmi_read_seeds *rows_dev, size_t cap_reads, uint32_t *occ_dev, uint64_t *offsets_dev, size_t cap_kmers,
+                                         uint64_t *values_dev, size_t cap_hits, uint64_t *n_reads, uint64_t *n_kmers, uint64_t *n_hits) {
+  return seed_reads_dist_entry(idx, comm, bytes_dev, n_bytes, true, max_occ, rows_dev, cap_reads, occ_dev, offsets_dev, cap_kmers, values_dev, cap_hits,
+                               n_reads, n_kmers, n_hits);
+}
+kmi_status kmi_index_seed_reads_dist_host(kmi_index *idx, kmi_comm *comm, const uint8_t *bytes, size_t n_bytes, uint32_t max_occ, kmi_read_seeds *rows,
+                                          size_t cap_reads, uint32_t *occ, uint64_t *offsets, size_t cap_kmers, uint64_t *values, size_t cap_hits,
+                                          uint64_t *n_reads, uint64_t *n_kmers, uint64_t *n_hits) {
+  return seed_reads_dist_entry(idx, comm, bytes, n_bytes, false, max_occ, rows, cap_reads, occ, offsets, cap_kmers, values, cap_hits, n_reads, n_kmers,
+                               n_hits);
 }
 
 // ---- count spectrum and count filter (kmi_spectrum.h)

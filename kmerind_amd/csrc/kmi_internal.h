@@ -13,6 +13,9 @@
 
 namespace kmi {
 
+// output hits a workgroup of the segmented copy of kmi_query_dist.h owns (kmi_ctx_debug_counter 11: tests make segments cross it)
+constexpr int kSegCopyThreads = 256, kSegCopyPerThread = 8, kSegCopyTile = kSegCopyThreads * kSegCopyPerThread;
+
 enum WsSlot {
   WS_TILE_INFO = 0,   // per-tile scan records
   WS_TILE_BASE,       // per-tile line bases
@@ -69,6 +72,14 @@ enum WsSlot {
   WS_LOCATE_POS,      // locate / seed_reads (kmi_locate.h): entry positions of every fine bucket grouped by key, one u32 per index entry
   WS_LOCATE_SCAN,     // ... tile sums of the device-wide scans
   WS_LOCATE_OFF,      // ... offsets[] of a batch's windows, or of the host form's queries
+  WS_QD_PERM,         // queries in the caller's order over ranks (kmi_query_dist.h): perm[j] = the query that sits at routed place j
+  WS_QD_SLOT,         // ... slot[i] = the routed place of query i (the inverse of perm)
+  WS_QD_ANS,          // ... the answers (count / occ, 4 bytes) that came back, in routed order
+  WS_QD_OFFS,         // ... routed-order offsets rebuilt from the returned occ
+  WS_QD_VALS,         // ... the value words that came back: a CSR in routed order
+  WS_QD_RANS,         // ... owner side: count / occ of every received key
+  WS_QD_ROFFS,        // ... owner side: offsets over the received keys, all sources concatenated
+  WS_QD_RVALS,        // ... owner side: the listed value words of the received keys
   WS_NUM_SLOTS
 };
 
@@ -228,6 +239,7 @@ struct kmi_ctx {
   uint64_t lookup_npass = 0;     // the largest pass count a bucket used in the last lookup / profile / locate / seed_reads (kmi_ctx_debug_counter 8)
   uint64_t retain_fullest = 0;   // entries of the fullest bucket the last kmi_index_retain_counts met (kmi_ctx_debug_counter 9)
   uint64_t setops_npass = 0;     // the largest pass count a bucket used in the last kmi_index_compare / kmi_index_combine (kmi_ctx_debug_counter 10)
+  uint64_t qd_answered = 0;      // keys this rank answered as their owner in the last lookup / profile / locate / seed_reads over ranks (kmi_ctx_debug_counter 12)
   int fa_left_carry = -1;        // de Bruijn tuples of a FASTA block (kmi_dbg_build_fasta_range_dist_host): the raw byte of the sequence
                                  // character before the block's first one, the in-edge of its first window; -1: none
 };
