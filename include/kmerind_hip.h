@@ -400,8 +400,9 @@ kmi_status kmi_index_build_range_dist_host(kmi_index *idx, kmi_comm *comm, const
  * device, kmi_fasta_partition_dev) and enters the collective build with it. Works for comm.size() == 1 too. */
 kmi_status kmi_index_build_fasta_file_dist_host(kmi_index *idx, kmi_comm *comm, const uint8_t *bytes, size_t n_bytes);
 /* ... and with every rank holding only ITS byte range of the file (file.hpp:1436-1610 hands each rank 1/p of the file): bytes =
- * file bytes [buffer_offset, buffer_offset + n_bytes), of which the first nominal_bytes are the rank's block of the equal split
- * (block r = [n r / p, n (r + 1) / p)) and the rest look-ahead; prev_byte = the file byte before the buffer, -1 at the file
+ * file bytes [buffer_offset, buffer_offset + n_bytes), of which the first nominal_bytes are the rank's block of any tiling of the
+ * file in rank order (the blocks' lengths are gathered with their summaries: the equal split, block r = [n r / p, n (r + 1) / p),
+ * is one such tiling; blocks may be empty) and the rest look-ahead; prev_byte = the file byte before the buffer, -1 at the file
  * start. What a block cannot know from its own bytes -- the kind of line its first byte sits on, the records that start before it,
  * whether the file opens with a header (fasta_loader.hpp:232-456) -- comes from the ranks' block summaries
  * (kmi_fasta_block_summary_dev), gathered once over the communicator and composed left to right. *need_more = 1 (returned BEFORE
