@@ -284,6 +284,36 @@ class NodeIndex {
   // (unitigs, bases) over all ranks of the last unitigs() call
   std::pair<uint64_t, uint64_t> unitigs_total() const { return std::make_pair(total_unitigs, total_bases); }
 
+  // ---- cleaning the map on the device (no counterpart in the reference; the definitions are in kmerind_hip.h).
+  // spectrum: out[min(occurrences, n_bins - 1)] = number of nodes with that many occurrences, over all ranks (collective when the
+  // object holds a communicator).
+  std::vector<uint64_t> spectrum(uint32_t n_bins = 256, kmi_spectrum_totals *totals = nullptr) const {
+    std::vector<uint64_t> out(n_bins, 0);
+    if (rccl) ::kmerind::check(ctx, kmi_dbg_spectrum_dist_host(g, rccl, n_bins, out.data(), totals));   // collective
+    else ::kmerind::check(ctx, kmi_dbg_spectrum_host(g, n_bins, out.data(), totals));
+    return out;
+  }
+  // retain_counts: keeps the nodes with lo <= occurrences <= hi; returns how many left THIS rank's part. Local on every rank
+  // (nothing is exchanged: a node lives on one rank); the survivors' neighbours keep their counters until prune_edges.
+  size_t retain_counts(uint32_t lo, uint32_t hi = UINT32_MAX) {
+    uint64_t n = 0;
+    ::kmerind::check(ctx, kmi_dbg_retain_counts(g, lo, hi, &n));
+    return (size_t)n;
+  }
+  // prune_edges: clears every edge counter that is below min_edge_count, leads to a k-mer that is not a node, or is not
+  // reciprocated by its neighbour. Returns the stats over all ranks (collective when the object holds a communicator); local, if
+  // given, receives this rank's.
+  kmi_dbg_prune_stats prune_edges(uint32_t min_edge_count = 1, kmi_dbg_prune_stats *local = nullptr) {
+    kmi_dbg_prune_stats mine{}, total{};
+    if (rccl) ::kmerind::check(ctx, kmi_dbg_prune_edges_dist_host(g, rccl, min_edge_count, &mine, &total));   // collective
+    else {
+      ::kmerind::check(ctx, kmi_dbg_prune_edges(g, min_edge_count, &mine));
+      total = mine;
+    }
+    if (local) *local = mine;
+    return total;
+  }
+
   kmi_ctx *context() const { return ctx; }
 
  private:

@@ -100,9 +100,9 @@ kmi_status kmi_ctx_reset_hints(kmi_ctx *ctx);
  * and 3: calls that reached hipMalloc; 4: blocks taken from the process-wide cache instead; 5: pointer-jumping rounds, 6: exchanges
  * and 7: bytes this rank sent in the context's last kmi_dbg_compact_dist_host; 8: the largest number of passes a bucket needed in
  * the context's last kmi_index_lookup_* / kmi_index_profile_reads_* / kmi_index_locate_* / kmi_index_seed_reads_* (1 when every
- * bucket's entries fit one table; 0: no bucket was looked at); 9: the entry count of the fullest bucket the context's last kmi_index_retain_counts met (0: the index was empty);
+ * bucket's entries fit one table; 0: no bucket was looked at); 9: the entry count of the fullest bucket the context's last kmi_index_retain_counts / kmi_dbg_retain_counts met (0: the index was empty);
  * 10: the largest number of passes a bucket needed in the context's last kmi_index_compare* / kmi_index_combine (0: no bucket
- * was looked at) */
+ * was looked at); 13: bytes this rank sent in the context's last kmi_dbg_prune_edges_dist_host */
 kmi_status kmi_ctx_debug_counter(const kmi_ctx *ctx, uint32_t which, uint64_t *value);
 /* A destroyed context leaves its large device blocks (workspace, spare index arrays: >= 1 MB each, 96 GB / 64 blocks at most) in a
  * process-wide cache per device, where the next context of that device finds them: its first build then does not wait for
@@ -854,6 +854,70 @@ kmi_status kmi_dbg_compact_dist_host(kmi_dbg *g, kmi_comm *comm, uint32_t min_ed
  * not been compacted since it last changed; KMI_ERR_OVERFLOW when a capacity is too small. */
 kmi_status kmi_dbg_unitigs_export_host(kmi_dbg *g, uint64_t *offsets, char *bases, uint64_t *occurrences, uint8_t *circular,
                                        size_t capacity_unitigs, size_t capacity_bases);
+
+/* ---- cleaning a node map: occurrence spectrum, filter by occurrences, edge pruning (no counterpart in the reference)
+ * Sequencing errors show up as nodes seen once or twice. The usual remedy is to drop them and to compact afterwards; rule 1 of the
+ * compaction above then still counts every survivor's counter towards a neighbour that has left (or that never was a node: an 'N'
+ * neighbour sets all four), and the unitig stops there. kmi_dbg_prune_edges is the explicit step that clears such counters.
+ *
+ * spectrum: the contract of kmi_index_spectrum_* (hist[min(c, n_bins - 1)], kmi_spectrum_totals, 2 <= n_bins <=
+ * KMI_SPECTRUM_MAX_BINS) applied to counts[8] of the nodes this rank holds; _dist_host (collective) sums over the ranks as
+ * kmi_index_spectrum_dist_host does. An EDGE_EXISTS map has no occurrence count: KMI_ERR_INVALID.
+ *
+ * retain_counts: keeps the nodes with lo <= counts[8] <= hi; the rest leave with their edge counters, as in kmi_dbg_erase_host.
+ * The survivors keep their eight counters bit for bit and their order, in fresh arrays of exactly the surviving size; the
+ * neighbours' counters are not touched (that is prune_edges). *n_erased = nodes that left (may be NULL). lo > hi or an EDGE_EXISTS
+ * map: KMI_ERR_INVALID. Local on every rank (a node lives on exactly one rank, so the union over the ranks is filtered when every
+ * rank has filtered its share; no _dist form). On any error the map holds what it held, and so does the result of an earlier
+ * compaction; a call that succeeds drops it.
+ *
+ * prune_edges, with t = min_edge_count >= 1. A counter is (v, E, b): v a node in its stored, canonical orientation, E out or in, b
+ * a base. Its neighbour k-mer is x = v[1..k-1] + b for E = out and x = b + v[0..k-2] for E = in; w = canonical(x). Its reciprocal
+ * counter is at w:
+ *      E     w stored as x         w stored as rc(x)
+ *      out   (w, in,  v[0])        (w, out, comp(v[0]))
+ *      in    (w, out, v[k-1])      (w, in,  comp(v[k-1]))
+ * Self-loops and hairpins follow the same formula (a hairpin's counter is its own reciprocal). Counters are read as the compaction
+ * reads them: 0 / 1 for an EDGE_EXISTS map. Every counter that is not 0 is judged against the map AS IT WAS WHEN THE CALL BEGAN,
+ * by the first rule that applies:
+ *  1. Weak. counter < t: cleared.
+ *  2. Absent. w is not a node: cleared.
+ *  3. Unreciprocated. The reciprocal counter is < t: cleared. Not applied when v or w is its own reverse complement (even k only):
+ *     an adjacency of a palindromic node lands in out[b] or in in[comp(b)] depending on the strand it was read from, so no single
+ *     counter reciprocates it. Rules 1 and 2 still apply.
+ *  4. Kept. Otherwise the counter keeps its value.
+ * Consequences: the result is a pure function of the map at the call; a second call with the same t clears nothing (for nodes that
+ * are not palindromes the reciprocal of the reciprocal is the counter itself); after prune(t), kmi_dbg_compact gives the same
+ * unitigs for every threshold 1..t; nodes are never removed and counts[8] never changes.
+ * KMI_ERR_INVALID: t = 0; an alphabet that is not 2-bit (the limit of the compaction); kmi_dbg_prune_edges on a map that holds one
+ * rank's share of a build over ranks. An empty map gives zeros. On any error the map holds what it held, and so does the result of
+ * an earlier compaction; a call that succeeds drops it. The call is complete on return.
+ * _dist_host (collective): the graph is the union of the ranks' maps; a counter whose neighbour lives on another rank is judged by
+ * that rank (one request of (n_words + 1) x 8 bytes and one answer of 8 bytes per counter >= t, two exchanges). stats_local: this
+ * rank's nodes and counters; stats_total: the sums over the ranks, the same on every rank (either may be NULL). At most 256 ranks;
+ * a communicator of another context gives KMI_ERR_INVALID. Argument errors are every rank's alike and return before anything
+ * collective; a rank that fails on its own does not leave its peers waiting: the verdict is agreed on by an all-reduce before
+ * each of the two exchanges and again before the maps change, and the peers return KMI_ERR_PEER (an error of the transport inside an
+ * exchange is not such a failure: it is reported to every rank by the exchange itself). A one-rank communicator gives what
+ * kmi_dbg_prune_edges gives (with KMI_FORCE_DIST=1 through the code of several ranks, the rank being its own peer; n_requests then
+ * counts the requests it sent itself). kmi_ctx_debug_counter 13 gives the bytes this rank sent. */
+typedef struct {
+  uint64_t n_nodes;           /* nodes of the map (this rank's; _total: all ranks') */
+  uint64_t n_set_before;      /* counters that were not 0 */
+  uint64_t n_weak;            /* cleared by rule 1 */
+  uint64_t n_absent;          /* cleared by rule 2 */
+  uint64_t n_unreciprocated;  /* cleared by rule 3 */
+  uint64_t n_set_after;       /* = n_set_before - n_weak - n_absent - n_unreciprocated */
+  uint64_t n_isolated;        /* nodes whose eight counters are all 0 afterwards */
+  uint64_t n_requests;        /* neighbour requests this rank sent over the communicator: 0 in the one-rank call; under KMI_FORCE_DIST=1 the requests
+                                 the one rank sent to itself */
+} kmi_dbg_prune_stats;  /* 64 bytes */
+kmi_status kmi_dbg_spectrum_host(kmi_dbg *g, uint32_t n_bins, uint64_t *hist, kmi_spectrum_totals *totals /* may be NULL */);
+kmi_status kmi_dbg_spectrum_dist_host(kmi_dbg *g, kmi_comm *comm, uint32_t n_bins, uint64_t *hist, kmi_spectrum_totals *totals /* may be NULL */);
+kmi_status kmi_dbg_retain_counts(kmi_dbg *g, uint32_t lo, uint32_t hi, uint64_t *n_erased /* may be NULL */);
+kmi_status kmi_dbg_prune_edges(kmi_dbg *g, uint32_t min_edge_count, kmi_dbg_prune_stats *stats /* may be NULL */);
+kmi_status kmi_dbg_prune_edges_dist_host(kmi_dbg *g, kmi_comm *comm, uint32_t min_edge_count, kmi_dbg_prune_stats *stats_local,
+                                         kmi_dbg_prune_stats *stats_total);
 
 /* ---- measurement support --------------------------------------------------- */
 /* per-kernel HIP-event timing on the context's stream (bench.py roofline leg) */

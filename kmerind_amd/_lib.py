@@ -55,6 +55,11 @@ class SpectrumTotals(C.Structure):
 SPECTRUM_MAX_BINS = 65536
 
 
+class DbgPruneStats(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("n_nodes", "n_set_before", "n_weak", "n_absent", "n_unreciprocated", "n_set_after", "n_isolated",
+                                          "n_requests")]
+
+
 class IndexOverlap(C.Structure):
     _fields_ = [("n_a", C.c_uint64), ("n_b", C.c_uint64), ("n_shared", C.c_uint64), ("sum_a", C.c_uint64), ("sum_b", C.c_uint64),
                 ("sum_a_shared", C.c_uint64), ("sum_b_shared", C.c_uint64), ("sum_min_shared", C.c_uint64)]
@@ -214,6 +219,11 @@ SIGNATURES = {
     "kmi_dbg_erase_dist_host": (C.c_int, [_P, _P, _P, _sz, C.POINTER(_u64)]),
     "kmi_dbg_count_dist_host": (C.c_int, [_P, _P, _P, _sz, C.POINTER(Results)]),
     "kmi_dbg_size_dist": (C.c_int, [_P, _P, C.POINTER(_u64)]),
+    "kmi_dbg_spectrum_host": (C.c_int, [_P, _u32, _P, C.POINTER(SpectrumTotals)]),
+    "kmi_dbg_spectrum_dist_host": (C.c_int, [_P, _P, _u32, _P, C.POINTER(SpectrumTotals)]),
+    "kmi_dbg_retain_counts": (C.c_int, [_P, _u32, _u32, C.POINTER(_u64)]),
+    "kmi_dbg_prune_edges": (C.c_int, [_P, _u32, C.POINTER(DbgPruneStats)]),
+    "kmi_dbg_prune_edges_dist_host": (C.c_int, [_P, _P, _u32, C.POINTER(DbgPruneStats), C.POINTER(DbgPruneStats)]),
     "kmi_dbg_compact": (C.c_int, [_P, _u32, C.POINTER(_u64), C.POINTER(_u64)]),
     "kmi_dbg_compact_dist_host": (C.c_int, [_P, _P, _u32, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
     "kmi_dbg_unitigs_export_host": (C.c_int, [_P, _P, _P, _P, _P, _sz, _sz]),

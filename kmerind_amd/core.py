@@ -708,6 +708,42 @@ class DeBruijnNodes:
                                                        nu.value, nb.value))
         return offsets, bases[:nb.value], occ[:nu.value], circ[:nu.value].astype(bool)
 
+    # ---- cleaning the map on the device (kmi_dbg_spectrum_* / kmi_dbg_retain_counts / kmi_dbg_prune_edges*)
+    def spectrum(self, n_bins=256, comm=None):
+        """(hist, totals) of the nodes' occurrence counts (counts[8]): hist[min(count, n_bins - 1)] counts the nodes
+        (np.uint64[n_bins]); totals is a dict of n_entries, sum_counts, min_count, max_count. With `comm` the call is collective and
+        both are summed over the ranks (kmi_dbg_spectrum_dist_host)."""
+        hist = np.ones(max(int(n_bins), 0), dtype=np.uint64)
+        t = L.SpectrumTotals()
+        if comm is not None:
+            self.ctx.check(lib.kmi_dbg_spectrum_dist_host(self.h, comm.h, n_bins, hist.ctypes.data_as(C.c_void_p), C.byref(t)))
+        else:
+            self.ctx.check(lib.kmi_dbg_spectrum_host(self.h, n_bins, hist.ctypes.data_as(C.c_void_p), C.byref(t)))
+        return hist, {"n_entries": t.n_entries, "sum_counts": t.sum_counts, "min_count": t.min_count, "max_count": t.max_count}
+
+    def retain_counts(self, lo, hi=2**32 - 1):
+        """keeps the nodes with lo <= occurrences <= hi, on the device; the rest leave with their edge counters (their neighbours'
+        counters stay: prune_edges) -> number of nodes erased. Local on every rank of a map held over ranks."""
+        n = C.c_uint64()
+        self.ctx.check(lib.kmi_dbg_retain_counts(self.h, lo, hi, C.byref(n)))
+        return n.value
+
+    def prune_edges(self, min_edge_count=1, comm=None):
+        """Clears every edge counter that is below min_edge_count, leads to a k-mer that is not a node, or is not reciprocated by
+        its neighbour (kmi_dbg_prune_edges; the definition is in include/kmerind_hip.h) -> dict of the kmi_dbg_prune_stats words.
+        With `comm` the call is collective over the union of the ranks' maps (kmi_dbg_prune_edges_dist_host): the dict is this
+        rank's and the sums over the ranks are left in `self.prune_totals`."""
+        names = [f for f, _ in L.DbgPruneStats._fields_]
+        s = L.DbgPruneStats()
+        if comm is not None:
+            tot = L.DbgPruneStats()
+            self.ctx.check(lib.kmi_dbg_prune_edges_dist_host(self.h, comm.h, int(min_edge_count), C.byref(s), C.byref(tot)))
+            self.prune_totals = {f: getattr(tot, f) for f in names}
+        else:
+            self.ctx.check(lib.kmi_dbg_prune_edges(self.h, int(min_edge_count), C.byref(s)))
+            self.prune_totals = {f: getattr(s, f) for f in names}
+        return {f: getattr(s, f) for f in names}
+
     def unitig_sequences(self, min_edge_count=1, comm=None):
         """the sequences of unitigs() as a list of bytes, in unitig order"""
         return split_unitigs(*self.unitigs(min_edge_count, comm)[:2])

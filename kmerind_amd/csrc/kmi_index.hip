@@ -3676,6 +3676,7 @@ static kmi_status merge_impl(kmi_index *idx, uint32_t nparts, const uint64_t *ke
 #include "kmi_lookup.h"
 #include "kmi_locate.h"
 #include "kmi_spectrum.h"
+#include "kmi_dbg_clean.h"
 #include "kmi_setops.h"
 
 struct kmi_comm;
@@ -5582,6 +5583,55 @@ kmi_status kmi_index_retain_counts(kmi_index *idx, uint32_t lo, uint32_t hi, uin
   if (!idx->has_data || idx->n_entries == 0) return KMI_OK;
   KMI_HIP(ctx, hipSetDevice(ctx->device));
   return index_retain_counts(idx, lo, hi, n_erased);
+}
+
+// ---- cleaning a de Bruijn node map (kmi_dbg_clean.h)
+// the node index is a count index whose values are the occurrences: its own spectrum entry points do the work
+static kmi_status dbg_has_occurrences(kmi_dbg *g) {
+  if (g->node_kind == KMI_DBG_EDGE_EXISTS) return set_err(g->ctx, KMI_ERR_INVALID, "spectrum: an EDGE_EXISTS map keeps no occurrence count");
+  return KMI_OK;
+}
+kmi_status kmi_dbg_spectrum_host(kmi_dbg *g, uint32_t n_bins, uint64_t *hist, kmi_spectrum_totals *totals) {
+  if (!g) return KMI_ERR_INVALID;
+  KMI_TRY(dbg_has_occurrences(g));
+  return kmi_index_spectrum_host(g->nodes, n_bins, hist, totals);
+}
+
+kmi_status kmi_dbg_spectrum_dist_host(kmi_dbg *g, kmi_comm *comm, uint32_t n_bins, uint64_t *hist, kmi_spectrum_totals *totals) {
+  if (!g) return KMI_ERR_INVALID;
+  KMI_TRY(dist_check(g->nodes, comm));
+  KMI_TRY(dbg_has_occurrences(g));   // (every rank's alike: nothing collective has started)
+  return kmi_index_spectrum_dist_host(g->nodes, comm, n_bins, hist, totals);
+}
+
+kmi_status kmi_dbg_retain_counts(kmi_dbg *g, uint32_t lo, uint32_t hi, uint64_t *n_erased) {
+  if (!g) return KMI_ERR_INVALID;
+  return kmi::dbg_retain_counts(g, lo, hi, n_erased);
+}
+
+kmi_status kmi_dbg_prune_edges(kmi_dbg *g, uint32_t min_edge_count, kmi_dbg_prune_stats *stats) {
+  if (!g) return KMI_ERR_INVALID;
+  uint64_t s[8];
+  const kmi_status st = kmi::dbg_prune(g, min_edge_count, s);
+  if (stats) memcpy(stats, s, sizeof(s));
+  return st;
+}
+
+kmi_status kmi_dbg_prune_edges_dist_host(kmi_dbg *g, kmi_comm *comm, uint32_t min_edge_count, kmi_dbg_prune_stats *stats_local,
+                                         kmi_dbg_prune_stats *stats_total) {
+  if (!g) return KMI_ERR_INVALID;
+  if (stats_local) memset(stats_local, 0, sizeof(*stats_local));
+  if (stats_total) memset(stats_total, 0, sizeof(*stats_total));
+  KMI_TRY(dist_check(g->nodes, comm));
+  uint64_t sl[8], stt[8];
+  kmi_status st;
+  if (kmi::comm_size(comm) == 1 && !g->ctx->force_dist) {
+    st = kmi::dbg_prune(g, min_edge_count, sl);
+    memcpy(stt, sl, sizeof(sl));
+  } else st = kmi::dbg_prune_dist(g, comm, min_edge_count, sl, stt);
+  if (stats_local) memcpy(stats_local, sl, sizeof(sl));
+  if (stats_total) memcpy(stats_total, stt, sizeof(stt));
+  return st;
 }
 
 // ---- two count indexes compared and combined (kmi_setops.h)

@@ -140,13 +140,16 @@ __global__ __launch_bounds__(kRetainCountThreads) void bucket_retain_count_kerne
 }
 
 // Fine bucket b: its surviving entries, in their old order, to new_off[b] of the new arrays. A tile is one entry per thread; a
-// bucket of more entries takes several tiles, each behind the survivors of the ones before it.
+// bucket of more entries takes several tiles, each behind the survivors of the ones before it. rows (null for a count index): a
+// 32-byte payload per entry, in the order of the keys -- the edge counters of a de Bruijn node map (kmi_dbg_retain_counts) --
+// which moves with its entry as two uint4.
 constexpr int kRetainTile = 256;
 template <int NW>
 __global__ __launch_bounds__(kRetainTile) void bucket_retain_compact_kernel(const uint64_t *__restrict__ keys, const uint32_t *__restrict__ vals,
                                                                            const uint64_t *__restrict__ idx_off, const uint32_t *__restrict__ idx_cnt,
                                                                            uint32_t lo, uint32_t hi, const uint64_t *__restrict__ new_off,
-                                                                           uint64_t *__restrict__ new_keys, uint32_t *__restrict__ new_vals) {
+                                                                           uint64_t *__restrict__ new_keys, uint32_t *__restrict__ new_vals,
+                                                                           const uint4 *__restrict__ rows, uint4 *__restrict__ new_rows) {
   __shared__ uint32_t s_scan[kRetainTile / kWave + 2];
   const uint32_t b = blockIdx.x;
   uint64_t dst = new_off[b];
@@ -165,6 +168,7 @@ __global__ __launch_bounds__(kRetainTile) void bucket_retain_compact_kernel(cons
 #pragma unroll
       for (int w = 0; w < NW; ++w) new_keys[o * NW + w] = keys[i * NW + w];
       new_vals[o] = c;
+      if (rows) { new_rows[o * 2u] = rows[i * 2u]; new_rows[o * 2u + 1u] = rows[i * 2u + 1u]; }
     }
     dst += total;
   }
@@ -210,8 +214,11 @@ static kmi_status spectrum_totals(kmi_index *idx, kmi_spectrum_totals *totals) {
   return KMI_OK;
 }
 
+// rows / new_rows: the payload of bucket_retain_compact_kernel. *new_rows stays null when nothing leaves (the index and the rows
+// stay as they are); else it is a fresh pool block of *new_rows_bytes, the caller's from then on.
 template <int NW, int BITS>
-static kmi_status retain_counts_impl(kmi_index *idx, uint32_t lo, uint32_t hi, uint64_t *n_erased) {
+static kmi_status retain_counts_impl(kmi_index *idx, uint32_t lo, uint32_t hi, uint64_t *n_erased, const uint32_t *rows, uint32_t **new_rows,
+                                     size_t *new_rows_bytes) {
   kmi_ctx *ctx = idx->ctx;
   void *p;
   KMI_TRY(ws_get(ctx, WS_SPECTRUM, sizeof(uint64_t) * SPEC_WORDS + sizeof(uint32_t) * kNumFine, &p));
@@ -246,9 +253,13 @@ static kmi_status retain_counts_impl(kmi_index *idx, uint32_t lo, uint32_t hi, u
   const size_t kb = (total ? total : 1) * NW * sizeof(uint64_t), vb = (total ? total : 1) * sizeof(uint32_t);
   hipError_t e1 = pool_alloc(ctx, (void **)&nk, kb);
   hipError_t e2 = pool_alloc(ctx, (void **)&nv, vb);
-  if (e1 != hipSuccess || e2 != hipSuccess) {
+  uint32_t *nr = nullptr;
+  const size_t rb = (total ? total : 1) * 8 * sizeof(uint32_t);
+  hipError_t e3 = rows ? pool_alloc(ctx, (void **)&nr, rb) : hipSuccess;
+  if (e1 != hipSuccess || e2 != hipSuccess || e3 != hipSuccess) {
     if (nk) pool_free(ctx, nk, kb);
     if (nv) pool_free(ctx, nv, vb);
+    if (nr) pool_free(ctx, nr, rb);
     pool_free(ctx, new_off, kOffBytes);
     return set_err(ctx, KMI_ERR_NOMEM, "hipMalloc failed for the index arrays");
   }
@@ -256,12 +267,13 @@ static kmi_status retain_counts_impl(kmi_index *idx, uint32_t lo, uint32_t hi, u
     ProfScope ps(ctx, "bucket_retain_compact", idx->n_entries);
     hipLaunchKernelGGL((bucket_retain_compact_kernel<NW>), dim3(kNumFine), dim3(kRetainTile), 0, ctx->stream, (const uint64_t *)idx->keys,
                        (const uint32_t *)idx->vals, (const uint64_t *)idx->bucket_off, (const uint32_t *)idx->bucket_cnt, lo, hi,
-                       (const uint64_t *)new_off, nk, nv);
+                       (const uint64_t *)new_off, nk, nv, (const uint4 *)rows, (uint4 *)nr);
   }
   e = hipGetLastError();
   if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
   if (e != hipSuccess) {   // the index stays as it was
     pool_free(ctx, nk, kb); pool_free(ctx, nv, vb); pool_free(ctx, new_off, kOffBytes);
+    if (nr) pool_free(ctx, nr, rb);
     return set_err(ctx, KMI_ERR_DEVICE, "retain_counts: %s", hipGetErrorString(e));
   }
   // the old arrays go back to the pool as in densify_impl; layout_w, owner_lp, saturating and the configuration stay
@@ -274,10 +286,12 @@ static kmi_status retain_counts_impl(kmi_index *idx, uint32_t lo, uint32_t hi, u
   idx->keys_bytes = kb; idx->vals_bytes = vb;
   if (n_erased) *n_erased = idx->n_entries - total;
   idx->n_entries = total;
+  if (rows) { *new_rows = nr; *new_rows_bytes = rb; }
   return KMI_OK;
 }
-static kmi_status index_retain_counts(kmi_index *idx, uint32_t lo, uint32_t hi, uint64_t *n_erased) {
-  KMI_DISPATCH(idx->shape, retain_counts_impl, idx, lo, hi, n_erased);
+static kmi_status index_retain_counts(kmi_index *idx, uint32_t lo, uint32_t hi, uint64_t *n_erased, const uint32_t *rows = nullptr,
+                                      uint32_t **new_rows = nullptr, size_t *new_rows_bytes = nullptr) {
+  KMI_DISPATCH(idx->shape, retain_counts_impl, idx, lo, hi, n_erased, rows, new_rows, new_rows_bytes);
 }
 
 }  // namespace kmi

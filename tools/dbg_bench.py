@@ -11,7 +11,17 @@ Unitigs over ranks: N processes share the GPU over a gloo group (kmerind_amd/tra
 them); every rank builds its share of the reads collectively, then kmi_dbg_compact_dist_host is timed warm, with its jumping rounds,
 exchanges, bytes exchanged per node and per-kernel times of rank 0. The transport stages every message through pinned host memory
 and gloo, so these are not RCCL numbers. Default input: 1 M reads of a 10 Mbp genome (1e7 nodes), k = 31. --out FILE: the figures as JSON.
-  python tools/dbg_bench.py --unitigs --ranks N [--out FILE] [reads] [genome] [k]"""
+  python tools/dbg_bench.py --unitigs --ranks N [--out FILE] [reads] [genome] [k]
+Cleaning: the same FASTQ input with substitutions put into the sequence lines on the host (numpy, seeded, default 0.5 % per base), so
+that singleton nodes exist; then spectrum, retain_counts(2), prune_edges(1), each timed warm on a second build with per-kernel times,
+and the unitig count and N50 as built, after the filter and after pruning. Yardsticks in the same run: unitig_table + unitig_links of
+kmi_dbg_compact on the map prune_edges runs on, and device-to-device copies of the bytes the row compaction needs (lower bound) and
+of every old entry read whole (upper bound of what it fetches).
+  python tools/dbg_bench.py --clean [--rate R] [reads] [genome] [k]
+Cleaning over ranks: N processes share the GPU over a gloo group as for --unitigs --ranks (staging through pinned host memory: not an
+interconnect); retain on every rank's share, kmi_dbg_prune_edges_dist_host timed warm, bytes exchanged per node, the slowest rank's
+wall time. Default input: 1 M reads of a 10 Mbp genome, k = 31.
+  python tools/dbg_bench.py --clean --ranks N [--rate R] [--out FILE] [reads] [genome] [k]"""
 import ctypes as C
 import os
 import sys
@@ -209,7 +219,197 @@ def main_unitigs_ranks(argv):
             f.write("\n")
 
 
+def with_substitutions(host, n_reads, rate, seed=11, read_len=150):
+    """the FASTQ buffer of K.synth_fastq with substitutions in the sequence lines: every base changes to the next letter with
+    probability `rate` (the number of changes is drawn once, their places uniformly)"""
+    rec = host.size // n_reads
+    off = int(np.flatnonzero(host[:rec] == ord("\n"))[0]) + 1   # the sequence line follows the header
+    assert host.size == rec * n_reads and host[off + read_len] == ord("\n")
+    rng = np.random.default_rng(seed)
+    n_err = int(rng.binomial(n_reads * read_len, rate))
+    at = rng.integers(0, n_reads * read_len, n_err, dtype=np.int64)
+    pos = (at // read_len) * rec + off + at % read_len
+    nxt = np.arange(256, dtype=np.uint8)
+    for a, b in zip(b"ACGT", b"CGTA"):
+        nxt[a] = b
+    host = host.copy()
+    host[pos] = nxt[host[pos]]
+    return host, n_err
+
+
+def _n50(off):
+    lens = np.sort(np.diff(off.astype(np.int64)))[::-1]
+    return int(lens[np.searchsorted(np.cumsum(lens), lens.sum() / 2)]) if lens.size else 0
+
+
+def _flag(argv, name, default, conv):
+    if name in argv:
+        i = argv.index(name)
+        v = conv(argv[i + 1])
+        del argv[i:i + 2]
+        return v
+    return default
+
+
+def main_clean(argv):
+    argv = list(argv)
+    rate = _flag(argv, "--rate", 0.005, float)
+    n_reads = int(argv[0]) if len(argv) > 0 else 10_000_000
+    genome = int(argv[1]) if len(argv) > 1 else 100_000_000
+    k = int(argv[2]) if len(argv) > 2 else 31
+    host, n_err = with_substitutions(np.asarray(K.synth_fastq(seed=2, genome_len=genome, n_reads=n_reads)), n_reads, rate)
+    dev = torch.device("cuda", 0)
+    d = torch.from_numpy(host).to(dev)
+    ctx = K.Context(0, stream=torch.cuda.current_stream(dev).cuda_stream)
+    g = K.DeBruijnNodes(ctx, K.make_config(k))
+    print("cleaning a de Bruijn node map, k=%d, %d reads over %d bp, %d substitutions (%.3g per base, seeded); one run on one GPU"
+          % (k, n_reads, genome, n_err, rate))
+
+    def kernels():
+        prof = {p["name"]: round(p["total_ms"], 3) for p in sorted(ctx.profile_get(), key=lambda p: -p["total_ms"]) if p["launches"]}
+        ctx.profile_reset()
+        return prof
+
+    def step(name, fn):
+        torch.cuda.synchronize()
+        ctx.profile_reset()
+        t0 = time.perf_counter()
+        r = fn()
+        torch.cuda.synchronize()
+        ms = (time.perf_counter() - t0) * 1e3
+        prof = kernels()
+        print("%-28s %9.2f ms  %s" % (name, ms, prof), flush=True)
+        return r, prof
+
+    for run in ("warm-up", "timed"):
+        g.clear(); g.build_device(d.data_ptr(), host.size)
+        torch.cuda.synchronize()
+        ctx.profile(run == "timed"); ctx.profile_reset()
+        if run == "timed":
+            print("-- second build, every step timed once (wall time with the host's part, then the kernels' own times)")
+        quiet = (lambda name, fn: (fn(), {})) if run == "warm-up" else step
+        n0 = g.local_size()
+        (hist, totals), _ = quiet("spectrum(256)", lambda: g.spectrum(256))
+        (off0, _, _, _), _ = quiet("unitigs, as built", lambda: g.unitigs(1))
+        erased, p_ret = quiet("retain_counts(2)", lambda: g.retain_counts(2))
+        n1 = g.local_size()
+        (off1, _, _, _), p_cmp = quiet("unitigs, after the filter", lambda: g.unitigs(1))
+        stats, p_pr = quiet("prune_edges(1)", lambda: g.prune_edges(1))
+        again, p_pr2 = quiet("prune_edges(1), second call", lambda: g.prune_edges(1))
+        (off2, _, _, _), _ = quiet("unitigs, after pruning", lambda: g.unitigs(1))
+    ctx.profile(False)
+    print("spectrum: bins 1..5 %s, totals %s" % (hist[1:6].tolist(), totals))
+    print("nodes %d -> %d (%d erased)" % (n0, n1, erased))
+    print("prune stats %s" % stats)
+    print("second call %s" % again)
+    for name, off in (("as built", off0), ("after retain_counts(2)", off1), ("after prune_edges(1)", off2)):
+        print("unitigs %-24s %10d, N50 %d" % (name, off.shape[0] - 1, _n50(off)))
+    # yardstick of the prune kernel: table + links of the compaction on the same map in the same run
+    links, table = p_cmp.get("unitig_links", float("nan")), p_cmp.get("unitig_table", float("nan"))
+    print("dbg_prune %.3f ms (second call %.3f ms) + unitig_table %.3f ms; kmi_dbg_compact on the same %d nodes: unitig_links %.3f ms + unitig_table %.3f ms;"
+          " dbg_prune / unitig_links = %.2f" % (p_pr.get("dbg_prune", float("nan")), p_pr2.get("dbg_prune", float("nan")), p_pr.get("unitig_table", float("nan")),
+                                                n1, links, table, p_pr.get("dbg_prune", float("nan")) / links))
+    # yardstick of the row compaction: a device-to-device copy of the bytes it reads and writes. The kernel reads the count of EVERY old
+    # entry (4 bytes) but the key and the row of the SURVIVORS alone, and writes key, count and row of the survivors: those are the
+    # bytes it needs. The survivors' keys and rows lie scattered among the others', so the memory system fetches more than that (whole
+    # sectors around an 8-byte key); how much has not been counted. Every old entry read whole is the upper bound of what it can fetch.
+    nw = g.n_words
+    needed = n0 * 4 + n1 * (8 * nw + 32) + n1 * (8 * nw + 4 + 32)
+    upper = n0 * (8 * nw + 4 + 32) + n1 * (8 * nw + 4 + 32)
+    g.close()
+    compact_ms = p_ret.get("bucket_retain_compact", float("nan"))
+    for name, moved in (("the bytes it needs (every old count; key and row of the survivors; the survivors written)", needed),
+                        ("the upper bound (every old entry read whole; the survivors written)", upper)):
+        a = torch.empty(moved // 2, dtype=torch.uint8, device=dev)
+        b = torch.empty_like(a)
+        b.copy_(a)
+        e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+        e0.record()
+        for _ in range(5):
+            b.copy_(a)
+        e1.record()
+        torch.cuda.synchronize()
+        copy_ms = e0.elapsed_time(e1) / 5
+        del a, b
+        print("bucket_retain_compact %.3f ms; %s: %d bytes read + written, device-to-device copy of as many %.3f ms (mean of 5), ratio %.2f"
+              % (compact_ms, name, moved, copy_ms, compact_ms / copy_ms))
+
+
+def _clean_ranks_worker(rank, world, port, n_reads, genome, k, rate, ret):
+    import torch.distributed as dist
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from kmerind_amd.transport import GroupComm
+        ctx = K.Context(0, rank=rank, nranks=world)
+        comm = GroupComm(ctx)
+        lo, hi = n_reads * rank // world, n_reads * (rank + 1) // world
+        host, _ = with_substitutions(np.asarray(K.synth_fastq(seed=2, genome_len=genome, n_reads=hi - lo, first_read=lo)), hi - lo, rate, seed=11 + rank)
+        g = K.DeBruijnNodes(ctx, K.make_config(k))
+        out = {}
+        for run in ("warm-up", "timed"):
+            g.clear(); g.build_dist(host, comm)
+            n0 = g.local_size()
+            hist, _ = g.spectrum(16, comm=comm)
+            erased = g.retain_counts(2)
+            ctx.profile(run == "timed"); ctx.profile_reset()
+            dist.barrier()
+            t0 = time.perf_counter()
+            stats = g.prune_edges(1, comm=comm)
+            wall = time.perf_counter() - t0
+            prof = {p["name"]: round(p["total_ms"], 3) for p in sorted(ctx.profile_get(), key=lambda p: -p["total_ms"]) if p["launches"]}
+            ctx.profile(False)
+            out = dict(nodes_built=n0, nodes=g.local_size(), erased=erased, prune_ms=wall * 1e3, stats=stats, total=dict(g.prune_totals), kernels_ms=prof,
+                       bytes_sent=ctx.debug_counter(13), hist=hist[:6].tolist())
+        g.unitigs(1, comm=comm)
+        out["unitigs_total"] = g.unitig_totals[0]
+        ret[rank] = out
+        g.close()
+        comm.close()
+        ctx.close()
+    finally:
+        dist.destroy_process_group()
+
+
+def main_clean_ranks(argv):
+    import json
+    import socket
+    import torch.multiprocessing as mp
+    argv = list(argv)
+    world = int(argv.pop(0))
+    rate = _flag(argv, "--rate", 0.005, float)
+    out_path = _flag(argv, "--out", None, str)
+    n_reads = int(argv[0]) if len(argv) > 0 else 1_000_000
+    genome = int(argv[1]) if len(argv) > 1 else 10_000_000
+    k = int(argv[2]) if len(argv) > 2 else 31
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    ret = mp.Manager().dict()
+    mp.spawn(_clean_ranks_worker, args=(world, port, n_reads, genome, k, rate, ret), nprocs=world, join=True)
+    res = [ret[r] for r in range(world)]
+    nodes = sum(r["nodes"] for r in res)
+    sent = sum(r["bytes_sent"] for r in res)
+    summary = dict(ranks=world, k=k, reads=n_reads, genome=genome, rate=rate, nodes_built=sum(r["nodes_built"] for r in res), nodes=nodes,
+                   nodes_per_rank=[r["nodes"] for r in res], prune_ms_per_rank=[round(r["prune_ms"], 1) for r in res], bytes_exchanged=sent,
+                   bytes_per_node=round(sent / max(nodes, 1), 1), stats_total=res[0]["total"], unitigs_total_after=res[0]["unitigs_total"],
+                   kernels_ms_rank0=res[0]["kernels_ms"], transport="gloo over pinned host staging (not an interconnect)")
+    print("cleaning over %d ranks (gloo transport, staging through pinned host memory: not an interconnect), k=%d, %d reads over %d bp, %d nodes after "
+          "retain_counts(2): kmi_dbg_prune_edges_dist_host %.1f ms warm on the slowest rank (one call), %.1f bytes exchanged per node"
+          % (world, k, n_reads, genome, nodes, max(summary["prune_ms_per_rank"]), summary["bytes_per_node"]))
+    print(json.dumps(summary))
+    if out_path:
+        with open(out_path, "w") as f:
+            json.dump(summary, f, indent=1)
+            f.write("\n")
+
+
 def main():
+    if len(sys.argv) > 3 and sys.argv[1] == "--clean" and sys.argv[2] == "--ranks":
+        return main_clean_ranks(sys.argv[3:])
+    if len(sys.argv) > 1 and sys.argv[1] == "--clean":
+        return main_clean(sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "--fasta":
         return main_fasta(sys.argv[2:])
     if len(sys.argv) > 3 and sys.argv[1] == "--unitigs" and sys.argv[2] == "--ranks":
