@@ -3686,14 +3686,75 @@ static kmi_status dist_state(kmi_index *idx, kmi_comm *comm, uint64_t *holders, 
 static kmi_status dist_agree(kmi_comm *comm, kmi_status mine);
 static int comm_rank_of(kmi_comm *comm);
 
+// ---- host glue that the entry points below share ------------------------------------------------------------------------
+// one rank and no KMI_FORCE_DIST: an entry over ranks takes the one-rank call
+static bool alone(kmi_ctx *ctx, kmi_comm *comm) { return kmi::comm_size(comm) == 1 && !ctx->force_dist; }
+
+// workspace slot `slot` of bytes + pad, and the bytes of a host buffer on their way into it on the context's stream (bytes == 0:
+// the slot alone). The caller's buffer must stay as it is until the stream has passed the copy.
+static kmi_status stage_host(kmi_ctx *ctx, kmi::WsSlot slot, const void *src, size_t bytes, size_t pad, void **dev) {
+  KMI_TRY(ws_get(ctx, slot, bytes + pad, dev));
+  if (bytes) KMI_HIP(ctx, hipMemcpyAsync(*dev, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+  return KMI_OK;
+}
+
+// n results of a query leave the device as malloc'd host arrays (kmi_results_free), key_bytes / val_bytes per result
+static kmi_status results_to_host(kmi_ctx *ctx, kmi_results *out, const void *d_keys, const void *d_vals, uint64_t n, size_t key_bytes,
+                                  size_t val_bytes) {
+  out->n = n;
+  out->keys = (uint64_t *)malloc((n ? n : 1) * key_bytes);
+  out->values = (uint64_t *)malloc((n ? n : 1) * val_bytes);
+  if (!out->keys || !out->values) return set_err(ctx, KMI_ERR_NOMEM, "host malloc failed");
+  if (n) {
+    KMI_HIP(ctx, hipMemcpyAsync(out->keys, d_keys, n * key_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    KMI_HIP(ctx, hipMemcpyAsync(out->values, d_vals, n * val_bytes, hipMemcpyDeviceToHost, ctx->stream));
+    KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  }
+  return KMI_OK;
+}
+
+// records (key words, value words) from separate arrays -- the layout of std::pair<Kmer, value>
+static void interleave_records(uint64_t *rec, const uint64_t *kmers, const uint64_t *values, size_t n, uint32_t nw, uint32_t vw) {
+  const uint32_t rw = nw + vw;
+  for (size_t i = 0; i < n; ++i) {
+    memcpy(rec + i * rw, kmers + i * nw, nw * sizeof(uint64_t));
+    memcpy(rec + i * rw + nw, values + i * vw, vw * sizeof(uint64_t));
+  }
+}
+
+// The bytes a rank read of a FASTQ file -- its nominal range + look-ahead, file bytes [buffer_offset, buffer_offset + n_bytes) -- staged
+// into `slot` and cut at record starts on the device: the rank's records are bytes [cut[0], cut[1]) of the buffer. *need_more = 1: no
+// record start behind the nominal end in what was read (nothing else has happened: the caller reads further and calls again).
+static kmi_status fastq_range_cut(kmi_ctx *ctx, kmi::WsSlot slot, const uint8_t *bytes, size_t n_bytes, uint64_t buffer_offset, uint64_t nominal_bytes,
+                                  int reaches_eof, void **d_bytes, uint64_t cut[2], int *need_more) {
+  if (nominal_bytes > n_bytes) nominal_bytes = n_bytes;
+  KMI_TRY(stage_host(ctx, slot, bytes, n_bytes, 64, d_bytes));
+  uint64_t pos[2] = {0, nominal_bytes};
+  cut[0] = 0; cut[1] = n_bytes;
+  if (n_bytes) {
+    KMI_TRY(kmi_fastq_find_records_dev(ctx, (const uint8_t *)*d_bytes, n_bytes, buffer_offset == 0, pos, 2, cut));
+    if (nominal_bytes >= n_bytes) cut[1] = n_bytes;   // (the nominal range is the rest of the buffer)
+  }
+  if (cut[1] >= n_bytes && !reaches_eof && n_bytes) { *need_more = 1; return KMI_OK; }   // no record start behind the nominal end in what was read
+  if (cut[0] >= n_bytes && !reaches_eof && n_bytes && buffer_offset != 0) { *need_more = 1; return KMI_OK; }
+  if (cut[1] < cut[0]) cut[1] = cut[0];
+  return KMI_OK;
+}
+
+// what the kmi_route_* / kmi_extract_route_* entries check first
+static kmi_status route_prologue(kmi_ctx *ctx, const kmi_config *cfg, KShape *shape, uint32_t nranks, const uint64_t *send_counts_host) {
+  if (!ctx) return KMI_ERR_INVALID;
+  if (!valid_config(cfg, shape)) return set_err(ctx, KMI_ERR_INVALID, "bad kmi_config");
+  if (nranks == 0 || nranks > (uint32_t)kNumCoarse || !send_counts_host) return set_err(ctx, KMI_ERR_INVALID, "nranks must be in 1..256");
+  return KMI_OK;
+}
+
 extern "C" {
 
 kmi_status kmi_route_tuples_dev(kmi_ctx *ctx, const kmi_config *cfg, const uint64_t *records_dev, size_t n, uint32_t nranks,
                                 uint32_t value_words, uint64_t *out_records_dev, uint64_t *send_counts_host) {
-  if (!ctx) return KMI_ERR_INVALID;
   KShape shape;
-  if (!valid_config(cfg, &shape)) return set_err(ctx, KMI_ERR_INVALID, "bad kmi_config");
-  if (nranks == 0 || nranks > (uint32_t)kNumCoarse || !send_counts_host) return set_err(ctx, KMI_ERR_INVALID, "nranks must be in 1..256");
+  KMI_TRY(route_prologue(ctx, cfg, &shape, nranks, send_counts_host));
   KMI_HIP(ctx, hipSetDevice(ctx->device));
   if (n == 0) { for (uint32_t r = 0; r < nranks; ++r) send_counts_host[r] = 0; return KMI_OK; }
   KMI_DISPATCH(shape, route_impl, ctx, cfg, shape, records_dev, n, nranks, value_words, out_records_dev, send_counts_host);
@@ -3701,22 +3762,14 @@ kmi_status kmi_route_tuples_dev(kmi_ctx *ctx, const kmi_config *cfg, const uint6
 
 kmi_status kmi_route_dev(kmi_ctx *ctx, const kmi_config *cfg, const uint64_t *keys_dev, size_t n, uint32_t nranks,
                          uint64_t *out_keys_dev, uint64_t *send_counts_host) {
-  if (!ctx) return KMI_ERR_INVALID;
-  KShape shape;
-  if (!valid_config(cfg, &shape)) return set_err(ctx, KMI_ERR_INVALID, "bad kmi_config");
-  if (nranks == 0 || nranks > (uint32_t)kNumCoarse || !send_counts_host) return set_err(ctx, KMI_ERR_INVALID, "nranks must be in 1..256");
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  if (n == 0) { for (uint32_t r = 0; r < nranks; ++r) send_counts_host[r] = 0; return KMI_OK; }
-  KMI_DISPATCH(shape, route_impl, ctx, cfg, shape, keys_dev, n, nranks, 0u, out_keys_dev, send_counts_host);
+  return kmi_route_tuples_dev(ctx, cfg, keys_dev, n, nranks, 0u, out_keys_dev, send_counts_host);   // (keys are records without value words)
 }
 
 kmi_status kmi_extract_route_dev(kmi_ctx *ctx, const kmi_config *cfg, const uint8_t *bytes_dev, size_t n_bytes, uint32_t nranks,
                                  uint64_t *out_keys_dev, size_t out_capacity, uint64_t *n_tuples, uint64_t *n_seqs,
                                  uint64_t *send_counts_host) {
-  if (!ctx) return KMI_ERR_INVALID;
   KShape shape;
-  if (!valid_config(cfg, &shape)) return set_err(ctx, KMI_ERR_INVALID, "bad kmi_config");
-  if (nranks == 0 || nranks > (uint32_t)kNumCoarse || !send_counts_host) return set_err(ctx, KMI_ERR_INVALID, "nranks must be in 1..256");
+  KMI_TRY(route_prologue(ctx, cfg, &shape, nranks, send_counts_host));
   if (cfg->seq_format != KMI_FMT_FASTQ) return set_err(ctx, KMI_ERR_INVALID, "extract_route: FASTQ only (use kmi_extract_dev + kmi_route_dev)");
   KMI_HIP(ctx, hipSetDevice(ctx->device));
   if (n_tuples) *n_tuples = 0;
@@ -3731,10 +3784,8 @@ kmi_status kmi_extract_route_dev(kmi_ctx *ctx, const kmi_config *cfg, const uint
 kmi_status kmi_extract_route_records_dev(kmi_ctx *ctx, const kmi_config *cfg, const uint8_t *bytes_dev, size_t n_bytes, uint64_t file_offset,
                                          uint32_t nranks, uint64_t *out_records_dev, size_t out_capacity, uint64_t *n_tuples, uint64_t *n_seqs,
                                          uint64_t *send_counts_host) {
-  if (!ctx) return KMI_ERR_INVALID;
   KShape shape;
-  if (!valid_config(cfg, &shape)) return set_err(ctx, KMI_ERR_INVALID, "bad kmi_config");
-  if (nranks == 0 || nranks > (uint32_t)kNumCoarse || !send_counts_host) return set_err(ctx, KMI_ERR_INVALID, "nranks must be in 1..256");
+  KMI_TRY(route_prologue(ctx, cfg, &shape, nranks, send_counts_host));
   if (cfg->index_kind == KMI_INDEX_COUNT) return set_err(ctx, KMI_ERR_INVALID, "records are the tuples of the position indexes (index_kind POSITION / POSQUAL)");
   if (cfg->index_kind == KMI_INDEX_POSQUAL && cfg->seq_format != KMI_FMT_FASTQ) return set_err(ctx, KMI_ERR_INVALID, "quality values need FASTQ input");
   KMI_HIP(ctx, hipSetDevice(ctx->device));
@@ -3781,19 +3832,22 @@ kmi_status kmi_index_destroy(kmi_index *idx) {
   return KMI_OK;
 }
 
-kmi_status kmi_index_insert_dev(kmi_index *idx, const uint64_t *kmers_dev, size_t n) {
+static kmi_status insert_entry(kmi_index *idx, const uint64_t *kmers, size_t n, bool transform, bool on_device) {
   if (!idx) return KMI_ERR_INVALID;
-  if (idx->val_words) return set_err(idx->ctx, KMI_ERR_INVALID, "a position index takes (k-mer, value) tuples: kmi_index_insert_tuples_*");
-  KMI_HIP(idx->ctx, hipSetDevice(idx->ctx->device));
-  return index_insert(idx, kmers_dev, n, true);
+  kmi_ctx *ctx = idx->ctx;
+  if (idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "a position index takes (k-mer, value) tuples: kmi_index_insert_tuples_*");
+  if (!on_device) {
+    if (n == 0) return KMI_OK;
+    if (!kmers) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
+  }
+  KMI_HIP(ctx, hipSetDevice(ctx->device));
+  void *din = nullptr;
+  if (!on_device) KMI_TRY(stage_host(ctx, WS_INPUT, kmers, n * idx->shape.n_words * sizeof(uint64_t), 0, &din));
+  return index_insert(idx, on_device ? kmers : (const uint64_t *)din, n, transform);
 }
-
-kmi_status kmi_index_insert_transformed_dev(kmi_index *idx, const uint64_t *kmers_dev, size_t n) {
-  if (!idx) return KMI_ERR_INVALID;
-  if (idx->val_words) return set_err(idx->ctx, KMI_ERR_INVALID, "a position index takes (k-mer, value) tuples: kmi_index_insert_tuples_*");
-  KMI_HIP(idx->ctx, hipSetDevice(idx->ctx->device));
-  return index_insert(idx, kmers_dev, n, false);
-}
+kmi_status kmi_index_insert_dev(kmi_index *idx, const uint64_t *kmers_dev, size_t n) { return insert_entry(idx, kmers_dev, n, true, true); }
+kmi_status kmi_index_insert_transformed_dev(kmi_index *idx, const uint64_t *kmers_dev, size_t n) { return insert_entry(idx, kmers_dev, n, false, true); }
+kmi_status kmi_index_insert_host(kmi_index *idx, const uint64_t *kmers, size_t n) { return insert_entry(idx, kmers, n, true, false); }
 
 kmi_status kmi_index_insert_pairs_dev(kmi_index *idx, const uint64_t *records_dev, size_t n) {
   if (!idx) return KMI_ERR_INVALID;
@@ -3810,24 +3864,8 @@ kmi_status kmi_index_insert_pairs_host(kmi_index *idx, const uint64_t *records, 
   if (!records) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
   KMI_HIP(ctx, hipSetDevice(ctx->device));
   void *din;
-  const size_t bytes = n * (idx->shape.n_words + 1) * sizeof(uint64_t);
-  KMI_TRY(ws_get(ctx, WS_INPUT, bytes, &din));
-  KMI_HIP(ctx, hipMemcpyAsync(din, records, bytes, hipMemcpyHostToDevice, ctx->stream));
+  KMI_TRY(stage_host(ctx, WS_INPUT, records, n * (idx->shape.n_words + 1) * sizeof(uint64_t), 0, &din));
   return index_insert_pairs(idx, (const uint64_t *)din, n, true, false);
-}
-
-kmi_status kmi_index_insert_host(kmi_index *idx, const uint64_t *kmers, size_t n) {
-  if (!idx) return KMI_ERR_INVALID;
-  kmi_ctx *ctx = idx->ctx;
-  if (idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "a position index takes (k-mer, value) tuples: kmi_index_insert_tuples_*");
-  if (n == 0) return KMI_OK;
-  if (!kmers) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  void *din;
-  const size_t bytes = n * idx->shape.n_words * sizeof(uint64_t);
-  KMI_TRY(ws_get(ctx, WS_INPUT, bytes, &din));
-  KMI_HIP(ctx, hipMemcpyAsync(din, kmers, bytes, hipMemcpyHostToDevice, ctx->stream));
-  return index_insert(idx, (const uint64_t *)din, n, true);
 }
 
 kmi_status kmi_index_set_seq_format(kmi_index *idx, uint32_t seq_format) {
@@ -3943,20 +3981,29 @@ kmi_status kmi_index_local_size(kmi_index *idx, uint64_t *n) {
   return KMI_OK;
 }
 
-kmi_status kmi_index_export_host(kmi_index *idx, uint64_t *keys, uint32_t *counts, size_t capacity, uint64_t *n) {
+// the entries to the host: keys, and counts (u32, a count index) or value words (tuples: a position index)
+static kmi_status export_entry(kmi_index *idx, bool tuples, uint64_t *keys, void *vals, size_t capacity, uint64_t *n) {
   if (!idx || !n) return KMI_ERR_INVALID;
   kmi_ctx *ctx = idx->ctx;
   *n = 0;
-  if (idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "a position index exports tuples: kmi_index_export_tuples_host");
+  if (tuples && idx->val_words == 0) return set_err(ctx, KMI_ERR_INVALID, "export_tuples needs a position index");
+  if (!tuples && idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "a position index exports tuples: kmi_index_export_tuples_host");
   if (idx->n_entries == 0) return KMI_OK;
   if (capacity < idx->n_entries) return set_err(ctx, KMI_ERR_OVERFLOW, "export: capacity too small");
   KMI_HIP(ctx, hipSetDevice(ctx->device));
   KMI_TRY(ensure_dense(idx));
+  const size_t val_bytes = tuples ? idx->val_words * sizeof(uint64_t) : sizeof(uint32_t);
   if (keys) KMI_HIP(ctx, hipMemcpyAsync(keys, idx->keys, idx->n_entries * idx->shape.n_words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (counts) KMI_HIP(ctx, hipMemcpyAsync(counts, idx->vals, idx->n_entries * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (vals) KMI_HIP(ctx, hipMemcpyAsync(vals, tuples ? (const void *)idx->mvals : (const void *)idx->vals, idx->n_entries * val_bytes, hipMemcpyDeviceToHost, ctx->stream));
   KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   *n = idx->n_entries;
   return KMI_OK;
+}
+kmi_status kmi_index_export_host(kmi_index *idx, uint64_t *keys, uint32_t *counts, size_t capacity, uint64_t *n) {
+  return export_entry(idx, false, keys, counts, capacity, n);
+}
+kmi_status kmi_index_export_tuples_host(kmi_index *idx, uint64_t *keys, uint64_t *values, size_t capacity, uint64_t *n) {
+  return export_entry(idx, true, keys, values, capacity, n);
 }
 
 void kmi_results_free(kmi_results *r) {
@@ -3976,8 +4023,7 @@ static kmi_status query_host(kmi_index *idx, int mode, const uint64_t *queries, 
   const uint32_t nw = idx->shape.n_words, ow = idx->val_words ? idx->val_words : 1u;
   const uint64_t bound = query_result_bound(idx, mode, nq);
   void *dq, *dk = nullptr, *dv = nullptr;
-  KMI_TRY(ws_get(ctx, WS_INPUT, nq * nw * sizeof(uint64_t), &dq));
-  KMI_HIP(ctx, hipMemcpyAsync(dq, queries, nq * nw * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+  KMI_TRY(stage_host(ctx, WS_INPUT, queries, nq * nw * sizeof(uint64_t), 0, &dq));
   const bool sized_inside = idx->val_words > 0 && mode == Q_FIND;   // a multimap find sizes its result buffers from a count of the hits
   if (mode != Q_ERASE && !sized_inside) {
     KMI_TRY(ws_get(ctx, WS_OUTPUT, (bound ? bound : 1) * nw * sizeof(uint64_t), &dk));
@@ -3987,16 +4033,7 @@ static kmi_status query_host(kmi_index *idx, int mode, const uint64_t *queries, 
   if (sized_inside) KMI_TRY(index_query(idx, mode, (const uint64_t *)dq, nq, nullptr, nullptr, 0, &n, (uint64_t **)&dk, (uint64_t **)&dv));
   else KMI_TRY(index_query(idx, mode, (const uint64_t *)dq, nq, (uint64_t *)dk, (uint64_t *)dv, bound, &n));
   if (mode == Q_ERASE) { if (n_erased) *n_erased = n; return KMI_OK; }
-  out->n = n;
-  out->keys = (uint64_t *)malloc((n ? n : 1) * nw * sizeof(uint64_t));
-  out->values = (uint64_t *)malloc((n ? n : 1) * ow * sizeof(uint64_t));
-  if (!out->keys || !out->values) return set_err(ctx, KMI_ERR_NOMEM, "host malloc failed");
-  if (n) {
-    KMI_HIP(ctx, hipMemcpyAsync(out->keys, dk, n * nw * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    KMI_HIP(ctx, hipMemcpyAsync(out->values, dv, n * ow * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return KMI_OK;
+  return results_to_host(ctx, out, dk, dv, n, nw * sizeof(uint64_t), ow * sizeof(uint64_t));
 }
 
 kmi_status kmi_index_count_host(kmi_index *idx, const uint64_t *queries, size_t nq, kmi_results *out) {
@@ -4046,13 +4083,9 @@ kmi_status kmi_index_insert_tuples_host(kmi_index *idx, const uint64_t *kmers, c
   if (!kmers || !values) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
   KMI_HIP(ctx, hipSetDevice(ctx->device));
   const uint32_t nw = idx->shape.n_words, vw = idx->val_words, rw = nw + vw;
-  // interleave into records (key words, value words) -- the layout of std::pair<Kmer, value>
   uint64_t *rec = (uint64_t *)malloc(n * rw * sizeof(uint64_t));
   if (!rec) return set_err(ctx, KMI_ERR_NOMEM, "host malloc failed");
-  for (size_t i = 0; i < n; ++i) {
-    memcpy(rec + i * rw, kmers + i * nw, nw * sizeof(uint64_t));
-    memcpy(rec + i * rw + nw, values + i * vw, vw * sizeof(uint64_t));
-  }
+  interleave_records(rec, kmers, values, n, nw, vw);
   void *din;
   kmi_status st = ws_get(ctx, WS_INPUT, n * rw * sizeof(uint64_t), &din);
   if (st == KMI_OK && hipMemcpy(din, rec, n * rw * sizeof(uint64_t), hipMemcpyHostToDevice) != hipSuccess)
@@ -4060,22 +4093,6 @@ kmi_status kmi_index_insert_tuples_host(kmi_index *idx, const uint64_t *kmers, c
   free(rec);
   if (st != KMI_OK) return st;
   return index_insert_records(idx, (const uint64_t *)din, n, true);
-}
-
-kmi_status kmi_index_export_tuples_host(kmi_index *idx, uint64_t *keys, uint64_t *values, size_t capacity, uint64_t *n) {
-  if (!idx || !n) return KMI_ERR_INVALID;
-  kmi_ctx *ctx = idx->ctx;
-  *n = 0;
-  if (idx->val_words == 0) return set_err(ctx, KMI_ERR_INVALID, "export_tuples needs a position index");
-  if (idx->n_entries == 0) return KMI_OK;
-  if (capacity < idx->n_entries) return set_err(ctx, KMI_ERR_OVERFLOW, "export: capacity too small");
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  KMI_TRY(ensure_dense(idx));
-  if (keys) KMI_HIP(ctx, hipMemcpyAsync(keys, idx->keys, idx->n_entries * idx->shape.n_words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (values) KMI_HIP(ctx, hipMemcpyAsync(values, idx->mvals, idx->n_entries * idx->val_words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-  KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  *n = idx->n_entries;
-  return KMI_OK;
 }
 
 uint32_t kmi_index_num_buckets(void) { return (uint32_t)kmi::kNumFine; }
@@ -4132,18 +4149,54 @@ static kmi_status dist_exchange(kmi_comm *comm, const void *send_dev, const uint
   return KMI_OK;
 }
 
+// where every routing of n host items starts: the items on their way into WS_INPUT, and WS_DIST_A for their copy grouped by destination
+static kmi_status stage_route_input(kmi_ctx *ctx, const void *items, size_t n, size_t item_bytes, void **d_in, void **d_send) {
+  KMI_TRY(ws_get(ctx, WS_INPUT, (n + 8) * item_bytes, d_in));
+  KMI_TRY(ws_get(ctx, WS_DIST_A, (n + 8) * item_bytes, d_send));
+  if (n) KMI_HIP(ctx, hipMemcpyAsync(*d_in, items, n * item_bytes, hipMemcpyHostToDevice, ctx->stream));
+  return KMI_OK;
+}
+
+// query keys to the ranks that own them: InputTransform + grouping by KeyToRank, or by the owner of the minimizer's bucket, and one
+// exchange. *d_recv (WS_DIST_B) = the keys that arrived, by source rank; rc = how many from each. (pairs_to_owners is its twin for records.)
+static kmi_status keys_to_owners(kmi_index *idx, kmi_comm *comm, const uint64_t *keys, size_t n, bool by_owner, void **d_recv,
+                                 std::vector<uint64_t> &rc, uint64_t *total) {
+  kmi_ctx *ctx = idx->ctx;
+  const int p = kmi::comm_size(comm);
+  const size_t kb = idx->shape.n_words * sizeof(uint64_t);
+  void *d_in, *d_send;
+  KMI_TRY(stage_route_input(ctx, keys, n, kb, &d_in, &d_send));
+  std::vector<uint64_t> sc(p, 0);
+  if (by_owner) KMI_TRY(kmi_route_owner_dev(ctx, &idx->cfg, (const uint64_t *)d_in, n, (uint32_t)p, (uint64_t *)d_send, sc.data()));
+  else KMI_TRY(kmi_route_dev(ctx, &idx->cfg, (const uint64_t *)d_in, n, (uint32_t)p, (uint64_t *)d_send, sc.data()));
+  return dist_exchange(comm, d_send, sc.data(), kb, WS_DIST_B, d_recv, rc, total);
+}
+
+// the answers of every source rank's keys back to their askers, keys (back[s] x kb bytes from d_rk) and values (x vb from d_rv) in two
+// exchanges, and from there to the host
+static kmi_status answers_to_askers(kmi_comm *comm, const void *d_rk, const void *d_rv, const std::vector<uint64_t> &back, size_t kb, size_t vb,
+                                    kmi_results *out) {
+  void *d_ak, *d_av;
+  uint64_t n_mine = 0, n_mine2 = 0;
+  std::vector<uint64_t> got;
+  KMI_TRY(dist_exchange(comm, d_rk, back.data(), kb, WS_DIST_A, &d_ak, got, &n_mine));
+  KMI_TRY(dist_exchange(comm, d_rv, back.data(), vb, WS_DIST_B, &d_av, got, &n_mine2));
+  kmi_ctx *ctx = kmi::comm_ctx(comm);
+  KMI_TRY(results_to_host(ctx, out, d_ak, d_av, n_mine, kb, vb));
+  if (n_mine == 0) KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));   // (a rank that is answered nothing still waits for what it sent)
+  return KMI_OK;
+}
+
 kmi_status kmi_index_insert_dist_host(kmi_index *idx, kmi_comm *comm, const uint64_t *kmers, size_t n) {
   KMI_TRY(dist_check(idx, comm));
   kmi_ctx *ctx = idx->ctx;
   if (idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "a position index takes (k-mer, value) tuples: kmi_index_insert_tuples_dist_host");
   if (n && !kmers) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
   const int p = kmi::comm_size(comm);
-  if (p == 1 && !ctx->force_dist) return kmi_index_insert_host(idx, kmers, n);
+  if (alone(ctx, comm)) return kmi_index_insert_host(idx, kmers, n);
   const size_t kb = idx->shape.n_words * sizeof(uint64_t);
   void *d_in, *d_send, *d_recv;
-  KMI_TRY(ws_get(ctx, WS_INPUT, (n + 8) * kb, &d_in));
-  KMI_TRY(ws_get(ctx, WS_DIST_A, (n + 8) * kb, &d_send));
-  if (n) KMI_HIP(ctx, hipMemcpyAsync(d_in, kmers, n * kb, hipMemcpyHostToDevice, ctx->stream));
+  KMI_TRY(stage_route_input(ctx, kmers, n, kb, &d_in, &d_send));
   std::vector<uint64_t> sc(p, 0), rc;
   // InputTransform + grouping by KeyToRank -- or by the owner of the minimizer's bucket when that is how the entries are distributed
   // (agreed over the ranks: a rank that happens to hold nothing must not route differently from its peers)
@@ -4164,13 +4217,10 @@ kmi_status kmi_index_insert_tuples_dist_host(kmi_index *idx, kmi_comm *comm, con
   if (idx->val_words == 0) return set_err(ctx, KMI_ERR_INVALID, "insert_tuples needs a position index");
   if (n && (!kmers || !values)) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
   const int p = kmi::comm_size(comm);
-  if (p == 1 && !ctx->force_dist) return kmi_index_insert_tuples_host(idx, kmers, values, n);
+  if (alone(ctx, comm)) return kmi_index_insert_tuples_host(idx, kmers, values, n);
   const uint32_t nw = idx->shape.n_words, vw = idx->val_words, rw = nw + vw;
   std::vector<uint64_t> rec((n + 1) * rw);
-  for (size_t i = 0; i < n; ++i) {
-    memcpy(&rec[i * rw], kmers + i * nw, nw * sizeof(uint64_t));
-    memcpy(&rec[i * rw + nw], values + i * vw, vw * sizeof(uint64_t));
-  }
+  interleave_records(rec.data(), kmers, values, n, nw, vw);
   void *d_in, *d_send, *d_recv;
   KMI_TRY(ws_get(ctx, WS_INPUT, (n + 8) * rw * sizeof(uint64_t), &d_in));
   KMI_TRY(ws_get(ctx, WS_DIST_A, (n + 8) * rw * sizeof(uint64_t), &d_send));
@@ -4191,9 +4241,7 @@ static kmi_status pairs_to_owners(kmi_index *idx, kmi_comm *comm, const uint64_t
   const int p = kmi::comm_size(comm);
   const uint32_t rw = idx->shape.n_words + 1;
   void *d_in, *d_send;
-  KMI_TRY(ws_get(ctx, WS_INPUT, (n + 8) * rw * sizeof(uint64_t), &d_in));
-  KMI_TRY(ws_get(ctx, WS_DIST_A, (n + 8) * rw * sizeof(uint64_t), &d_send));
-  if (n) KMI_HIP(ctx, hipMemcpyAsync(d_in, records, n * rw * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+  KMI_TRY(stage_route_input(ctx, records, n, rw * sizeof(uint64_t), &d_in, &d_send));
   uint64_t holders = 0, owner_p = 0, owner_any = 0;
   KMI_TRY(dist_state(idx, comm, &holders, &owner_p, &owner_any));
   const bool by_owner = owner_any != 0 && holders != 0;
@@ -4208,7 +4256,7 @@ kmi_status kmi_index_insert_pairs_dist_host(kmi_index *idx, kmi_comm *comm, cons
   kmi_ctx *ctx = idx->ctx;
   if (idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "(k-mer, count) pairs go into a count index");
   if (n && !records) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  if (kmi::comm_size(comm) == 1 && !ctx->force_dist) return kmi_index_insert_pairs_host(idx, records, n);
+  if (alone(ctx, comm)) return kmi_index_insert_pairs_host(idx, records, n);
   void *d_recv; uint64_t total = 0;
   KMI_TRY(pairs_to_owners(idx, comm, records, n, &d_recv, &total));
   const uint32_t lp = idx->owner_lp;
@@ -4230,12 +4278,10 @@ kmi_status kmi_index_route_pairs_dist_host(kmi_index *idx, kmi_comm *comm, const
   if (n && !records) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
   const uint32_t nw = idx->shape.n_words, rw = nw + 1;
   void *d_recv = nullptr; uint64_t total = 0;
-  if (kmi::comm_size(comm) == 1 && !ctx->force_dist) {
+  if (alone(ctx, comm)) {
     // one rank: the pairs with their keys transformed (route_pairs with one destination does exactly that)
     void *d_in, *d_send;
-    KMI_TRY(ws_get(ctx, WS_INPUT, (n + 8) * rw * sizeof(uint64_t), &d_in));
-    KMI_TRY(ws_get(ctx, WS_DIST_A, (n + 8) * rw * sizeof(uint64_t), &d_send));
-    if (n) KMI_HIP(ctx, hipMemcpyAsync(d_in, records, n * rw * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+    KMI_TRY(stage_route_input(ctx, records, n, rw * sizeof(uint64_t), &d_in, &d_send));
     uint64_t sc1 = 0;
     KMI_TRY(route_pairs(ctx, &idx->cfg, idx->shape, (const uint64_t *)d_in, n, 1u, false, (uint64_t *)d_send, &sc1));
     d_recv = d_send; total = n;
@@ -4263,7 +4309,7 @@ kmi_status kmi_index_update_pairs_dist_host(kmi_index *idx, kmi_comm *comm, cons
   if (idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "update() is a member of the counting maps");
   if (op > KMI_UPDATE_ASSIGN) return set_err(ctx, KMI_ERR_INVALID, "unknown updater");
   if (n && !records) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  if (kmi::comm_size(comm) == 1 && !ctx->force_dist) return kmi_index_update_pairs_host(idx, records, n, op, n_updated);
+  if (alone(ctx, comm)) return kmi_index_update_pairs_host(idx, records, n, op, n_updated);
   void *d_recv; uint64_t total = 0;
   KMI_TRY(pairs_to_owners(idx, comm, records, n, &d_recv, &total));   // (pairs of one key arrive in source-rank order, each source's in input order)
   if (total == 0) return KMI_OK;
@@ -4428,7 +4474,7 @@ kmi_status kmi_index_build_dist_dev(kmi_index *idx, kmi_comm *comm, const uint8_
   KMI_TRY(dist_check(idx, comm));
   kmi_ctx *ctx = idx->ctx;
   const int p = kmi::comm_size(comm);
-  if (p == 1 && !ctx->force_dist) return kmi_index_build_dev(idx, d_bytes, n_bytes, file_offset);
+  if (alone(ctx, comm)) return kmi_index_build_dev(idx, d_bytes, n_bytes, file_offset);
   if (n_bytes && !d_bytes) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
   const uint32_t nw = idx->shape.n_words, vw = idx->val_words, rw = nw + vw;
   void *d_send = nullptr, *d_recv;
@@ -4490,18 +4536,10 @@ kmi_status kmi_index_build_range_dist_host(kmi_index *idx, kmi_comm *comm, const
   *need_more = 0;
   if (n_bytes && !bytes) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
   if (idx->cfg.seq_format != KMI_FMT_FASTQ) return set_err(ctx, KMI_ERR_INVALID, "a byte range of a file is cut at FASTQ record starts here (a FASTA partition comes with kmi_ctx_set_fasta_partition)");
-  if (nominal_bytes > n_bytes) nominal_bytes = n_bytes;
   void *d_bytes;
-  KMI_TRY(ws_get(ctx, WS_INPUT, n_bytes + 64, &d_bytes));
-  uint64_t pos[2] = {0, nominal_bytes}, cut[2] = {0, n_bytes};
-  if (n_bytes) {
-    KMI_HIP(ctx, hipMemcpyAsync(d_bytes, bytes, n_bytes, hipMemcpyHostToDevice, ctx->stream));
-    KMI_TRY(kmi_fastq_find_records_dev(ctx, (const uint8_t *)d_bytes, n_bytes, buffer_offset == 0, pos, 2, cut));
-    if (nominal_bytes >= n_bytes) cut[1] = n_bytes;   // (the nominal range is the rest of the buffer)
-  }
-  if (cut[1] >= n_bytes && !reaches_eof && n_bytes) { *need_more = 1; return KMI_OK; }   // no record start behind the nominal end in what was read
-  if (cut[0] >= n_bytes && !reaches_eof && n_bytes && buffer_offset != 0) { *need_more = 1; return KMI_OK; }
-  if (cut[1] < cut[0]) cut[1] = cut[0];
+  uint64_t cut[2];
+  KMI_TRY(fastq_range_cut(ctx, WS_INPUT, bytes, n_bytes, buffer_offset, nominal_bytes, reaches_eof, &d_bytes, cut, need_more));
+  if (*need_more) return KMI_OK;
   return kmi_index_build_dist_dev(idx, comm, (const uint8_t *)d_bytes + cut[0], (size_t)(cut[1] - cut[0]), buffer_offset + cut[0]);
 }
 
@@ -4515,8 +4553,7 @@ kmi_status kmi_index_build_fasta_file_dist_host(kmi_index *idx, kmi_comm *comm, 
   if (n_bytes && !bytes) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
   const uint32_t p = (uint32_t)kmi::comm_size(comm), r = (uint32_t)kmi::comm_rank(comm);
   void *d_bytes;
-  KMI_TRY(ws_get(ctx, WS_INPUT, n_bytes + 64, &d_bytes));
-  if (n_bytes) KMI_HIP(ctx, hipMemcpyAsync(d_bytes, bytes, n_bytes, hipMemcpyHostToDevice, ctx->stream));
+  KMI_TRY(stage_host(ctx, WS_INPUT, bytes, n_bytes, 64, &d_bytes));
   std::vector<uint64_t> be(2 * (size_t)p);
   std::vector<kmi_fasta_partition> parts(p);
   KMI_TRY(kmi_fasta_partition_dev(ctx, (const uint8_t *)d_bytes, n_bytes, p, idx->shape.k, be.data(), parts.data()));
@@ -4608,8 +4645,7 @@ kmi_status kmi_index_build_fasta_range_dist_host(kmi_index *idx, kmi_comm *comm,
   if (idx->cfg.seq_format != KMI_FMT_FASTA) return set_err(ctx, KMI_ERR_INVALID, "not a FASTA index");
   if ((n_bytes && !bytes) || nominal_bytes > n_bytes) return set_err(ctx, KMI_ERR_INVALID, "bad buffer");
   void *d_bytes;
-  KMI_TRY(ws_get(ctx, WS_INPUT, n_bytes + 64, &d_bytes));
-  if (n_bytes) KMI_HIP(ctx, hipMemcpyAsync(d_bytes, bytes, n_bytes, hipMemcpyHostToDevice, ctx->stream));
+  KMI_TRY(stage_host(ctx, WS_INPUT, bytes, n_bytes, 64, &d_bytes));
   kmi_fasta_partition part; uint64_t end = 0;
   KMI_TRY(fasta_range_partition(ctx, comm, idx->shape.k - 1u, bytes, (const uint8_t *)d_bytes, n_bytes, buffer_offset, nominal_bytes, reaches_eof,
                                 prev_byte, need_more, &part, &end));
@@ -4632,8 +4668,7 @@ kmi_status kmi_extract_fasta_range_dist_host(kmi_ctx *ctx, const kmi_config *cfg
   if ((n_bytes && !bytes) || nominal_bytes > n_bytes) return set_err(ctx, KMI_ERR_INVALID, "bad buffer");
   KMI_HIP(ctx, hipSetDevice(ctx->device));
   void *d_bytes;
-  KMI_TRY(ws_get(ctx, WS_INPUT2, n_bytes + 64, &d_bytes));
-  if (n_bytes) KMI_HIP(ctx, hipMemcpyAsync(d_bytes, bytes, n_bytes, hipMemcpyHostToDevice, ctx->stream));
+  KMI_TRY(stage_host(ctx, WS_INPUT2, bytes, n_bytes, 64, &d_bytes));
   kmi_fasta_partition part; uint64_t end = 0;
   KMI_TRY(fasta_range_partition(ctx, comm, cfg->k - 1u, bytes, (const uint8_t *)d_bytes, n_bytes, buffer_offset, nominal_bytes, reaches_eof,
                                 prev_byte, need_more, &part, &end));
@@ -4647,11 +4682,10 @@ kmi_status kmi_extract_fasta_range_dist_host(kmi_ctx *ctx, const kmi_config *cfg
 kmi_status kmi_index_build_dist_host(kmi_index *idx, kmi_comm *comm, const uint8_t *bytes, size_t n_bytes, uint64_t file_offset) {
   KMI_TRY(dist_check(idx, comm));
   kmi_ctx *ctx = idx->ctx;
-  if (kmi::comm_size(comm) == 1 && !ctx->force_dist) return kmi_index_build_host(idx, bytes, n_bytes, file_offset);
+  if (alone(ctx, comm)) return kmi_index_build_host(idx, bytes, n_bytes, file_offset);
   if (n_bytes && !bytes) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
   void *d_bytes;
-  KMI_TRY(ws_get(ctx, WS_INPUT, n_bytes + 64, &d_bytes));
-  if (n_bytes) KMI_HIP(ctx, hipMemcpyAsync(d_bytes, bytes, n_bytes, hipMemcpyHostToDevice, ctx->stream));
+  KMI_TRY(stage_host(ctx, WS_INPUT, bytes, n_bytes, 64, &d_bytes));
   return kmi_index_build_dist_dev(idx, comm, (const uint8_t *)d_bytes, n_bytes, file_offset);
 }
 
@@ -4659,21 +4693,16 @@ static kmi_status query_dist_host(kmi_index *idx, kmi_comm *comm, int mode, cons
   KMI_TRY(dist_check(idx, comm));
   kmi_ctx *ctx = idx->ctx;
   const int p = kmi::comm_size(comm);
-  if (p == 1 && !ctx->force_dist) return query_host(idx, mode, queries, nq, out, n_erased);
+  if (alone(ctx, comm)) return query_host(idx, mode, queries, nq, out, n_erased);
   if (out) memset(out, 0, sizeof(*out));
   if (n_erased) *n_erased = 0;
   if (nq && !queries) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
   const uint32_t nw = idx->shape.n_words, ow = idx->val_words ? idx->val_words : 1u;
   const size_t kb = nw * sizeof(uint64_t), vb = ow * sizeof(uint64_t);
-  void *d_in, *d_send, *d_q;
-  KMI_TRY(ws_get(ctx, WS_INPUT, (nq + 8) * kb, &d_in));
-  KMI_TRY(ws_get(ctx, WS_DIST_A, (nq + 8) * kb, &d_send));
-  if (nq) KMI_HIP(ctx, hipMemcpyAsync(d_in, queries, nq * kb, hipMemcpyHostToDevice, ctx->stream));
-  std::vector<uint64_t> sc(p, 0), rc;
-  if (idx->owner_lp) KMI_TRY(kmi_route_owner_dev(ctx, &idx->cfg, (const uint64_t *)d_in, nq, (uint32_t)p, (uint64_t *)d_send, sc.data()));
-  else KMI_TRY(kmi_route_dev(ctx, &idx->cfg, (const uint64_t *)d_in, nq, (uint32_t)p, (uint64_t *)d_send, sc.data()));
+  void *d_q;
+  std::vector<uint64_t> rc;
   uint64_t total = 0;
-  KMI_TRY(dist_exchange(comm, d_send, sc.data(), kb, WS_DIST_B, &d_q, rc, &total));
+  KMI_TRY(keys_to_owners(idx, comm, queries, nq, idx->owner_lp != 0, &d_q, rc, &total));
   if (mode == Q_ERASE) {
     uint64_t n = 0;
     if (total) KMI_TRY(index_query(idx, Q_ERASE, (const uint64_t *)d_q, (size_t)total, nullptr, nullptr, 0, &n));
@@ -4683,7 +4712,7 @@ static kmi_status query_dist_host(kmi_index *idx, kmi_comm *comm, int mode, cons
   // every source rank's keys are answered on their own (a key two ranks ask about is answered to both). The answers of a multimap
   // find are sized by a count of the hits per source (a bound by the entries of the index, per source, is p times the index)
   const bool mm_find = idx->val_words > 0 && mode == Q_FIND;
-  std::vector<uint64_t> back(p, 0), got;
+  std::vector<uint64_t> back(p, 0);
   uint64_t bound = 0, off = 0;
   for (int s = 0; s < p; ++s) {
     if (mm_find) {
@@ -4704,20 +4733,7 @@ static kmi_status query_dist_host(kmi_index *idx, kmi_comm *comm, int mode, cons
                           mm_find ? back[s] : query_result_bound(idx, mode, (size_t)rc[s]), &n));
     back[s] = n; off += rc[s]; pos += n;
   }
-  void *d_ak, *d_av;
-  uint64_t n_mine = 0, n_mine2 = 0;
-  KMI_TRY(dist_exchange(comm, d_rk, back.data(), kb, WS_DIST_A, &d_ak, got, &n_mine));
-  KMI_TRY(dist_exchange(comm, d_rv, back.data(), vb, WS_DIST_B, &d_av, got, &n_mine2));
-  out->n = n_mine;
-  out->keys = (uint64_t *)malloc((n_mine ? n_mine : 1) * kb);
-  out->values = (uint64_t *)malloc((n_mine ? n_mine : 1) * vb);
-  if (!out->keys || !out->values) return set_err(ctx, KMI_ERR_NOMEM, "host malloc failed");
-  if (n_mine) {
-    KMI_HIP(ctx, hipMemcpyAsync(out->keys, d_ak, n_mine * kb, hipMemcpyDeviceToHost, ctx->stream));
-    KMI_HIP(ctx, hipMemcpyAsync(out->values, d_av, n_mine * vb, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return KMI_OK;
+  return answers_to_askers(comm, d_rk, d_rv, back, kb, vb, out);
 }
 
 kmi_status kmi_index_count_dist_host(kmi_index *idx, kmi_comm *comm, const uint64_t *queries, size_t nq, kmi_results *out) {
@@ -4829,8 +4845,7 @@ kmi_status kmi_dbg_build_host(kmi_dbg *g, const uint8_t *bytes, size_t n_bytes) 
   if (!bytes) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
   KMI_HIP(ctx, hipSetDevice(ctx->device));
   void *din;
-  KMI_TRY(ws_get(ctx, WS_INPUT, n_bytes + 64, &din));
-  KMI_HIP(ctx, hipMemcpyAsync(din, bytes, n_bytes, hipMemcpyHostToDevice, ctx->stream));
+  KMI_TRY(stage_host(ctx, WS_INPUT, bytes, n_bytes, 64, &din));
   return kmi_dbg_build_dev(g, (const uint8_t *)din, n_bytes);
 }
 
@@ -4841,30 +4856,23 @@ static kmi_status dbg_insert_tuples(kmi_dbg *g, uint64_t *recs_dev, size_t n) {
   return dbg_insert(g, recs_dev, n);
 }
 
-kmi_status kmi_dbg_insert_dev(kmi_dbg *g, const uint64_t *records_dev, size_t n) {
+static kmi_status dbg_insert_entry(kmi_dbg *g, const uint64_t *records, size_t n, bool on_device) {
   if (!g) return KMI_ERR_INVALID;
   kmi_ctx *ctx = g->ctx;
+  if (!on_device) {
+    if (n == 0) return KMI_OK;
+    if (!records) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
+  }
   KMI_HIP(ctx, hipSetDevice(ctx->device));
   if (n == 0) return KMI_OK;
   void *dr;   // (the caller's buffer stays as it is)
   const size_t bytes = n * (g->shape.n_words + 1) * sizeof(uint64_t);
   KMI_TRY(ws_get(ctx, WS_DBG_RECS, bytes + 64, &dr));
-  KMI_HIP(ctx, hipMemcpyAsync(dr, records_dev, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  KMI_HIP(ctx, hipMemcpyAsync(dr, records, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
   return dbg_insert_tuples(g, (uint64_t *)dr, n);
 }
-
-kmi_status kmi_dbg_insert_host(kmi_dbg *g, const uint64_t *records, size_t n) {
-  if (!g) return KMI_ERR_INVALID;
-  kmi_ctx *ctx = g->ctx;
-  if (n == 0) return KMI_OK;
-  if (!records) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  void *dr;
-  const size_t bytes = n * (g->shape.n_words + 1) * sizeof(uint64_t);
-  KMI_TRY(ws_get(ctx, WS_DBG_RECS, bytes + 64, &dr));
-  KMI_HIP(ctx, hipMemcpyAsync(dr, records, bytes, hipMemcpyHostToDevice, ctx->stream));
-  return dbg_insert_tuples(g, (uint64_t *)dr, n);
-}
+kmi_status kmi_dbg_insert_dev(kmi_dbg *g, const uint64_t *records_dev, size_t n) { return dbg_insert_entry(g, records_dev, n, true); }
+kmi_status kmi_dbg_insert_host(kmi_dbg *g, const uint64_t *records, size_t n) { return dbg_insert_entry(g, records, n, false); }
 
 kmi_status kmi_dbg_find_dev(kmi_dbg *g, const uint64_t *queries_dev, size_t nq, uint64_t *out_keys_dev, uint64_t *out_values_dev, uint64_t *n_out) {
   if (!g || !n_out) return KMI_ERR_INVALID;
@@ -4887,16 +4895,7 @@ kmi_status kmi_dbg_find_host(kmi_dbg *g, const uint64_t *queries, size_t nq, kmi
   KMI_HIP(ctx, hipMemcpyAsync(dq, queries, nq * nw * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
   uint64_t n = 0;
   KMI_TRY(dbg_find(g, (const uint64_t *)dq, nq, (uint64_t *)dk, (uint64_t *)dv, &n));
-  out->n = n;
-  out->keys = (uint64_t *)malloc((n ? n : 1) * nw * sizeof(uint64_t));
-  out->values = (uint64_t *)malloc((n ? n : 1) * kDbgValueWords * sizeof(uint64_t));
-  if (!out->keys || !out->values) return set_err(ctx, KMI_ERR_NOMEM, "host malloc failed");
-  if (n) {
-    KMI_HIP(ctx, hipMemcpyAsync(out->keys, dk, n * nw * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    KMI_HIP(ctx, hipMemcpyAsync(out->values, dv, n * kDbgValueWords * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-    KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  }
-  return KMI_OK;
+  return results_to_host(ctx, out, dk, dv, n, nw * sizeof(uint64_t), kDbgValueWords * sizeof(uint64_t));
 }
 
 kmi_status kmi_dbg_count_host(kmi_dbg *g, const uint64_t *queries, size_t nq, kmi_results *out) {
@@ -4929,21 +4928,14 @@ kmi_status kmi_dbg_export_host(kmi_dbg *g, uint64_t *keys, uint32_t *counts9, si
   return KMI_OK;
 }
 
-// build over ranks: parse the rank's share, group the node-form tuples by KeyToRank of the canonical k-mer, one all-to-all
-// (imxx::distribute inside de_bruijn_nodes_distributed::insert, de_bruijn_nodes_distributed.hpp:243-250), insert what arrives
-kmi_status kmi_dbg_build_dist_host(kmi_dbg *g, kmi_comm *comm, const uint8_t *bytes, size_t n_bytes) {
-  if (!g) return KMI_ERR_INVALID;
-  KMI_TRY(dist_check(g->nodes, comm));
+// the tail of the builds over ranks: nt node-form tuples grouped by KeyToRank of the canonical k-mer, one all-to-all, and what
+// arrives inserted (a rank without tuples still enters the exchange)
+static kmi_status dbg_route_exchange_insert(kmi_dbg *g, kmi_comm *comm, const uint64_t *recs, uint64_t nt) {
   kmi_ctx *ctx = g->ctx;
   const int p = kmi::comm_size(comm);
-  if (p == 1 && !ctx->force_dist) return kmi_dbg_build_host(g, bytes, n_bytes);
-  if (n_bytes && !bytes) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
   const uint32_t rw = g->shape.n_words + 1u;
-  void *d_bytes, *d_send, *d_recv;
-  KMI_TRY(ws_get(ctx, WS_INPUT, n_bytes + 64, &d_bytes));
-  if (n_bytes) KMI_HIP(ctx, hipMemcpyAsync(d_bytes, bytes, n_bytes, hipMemcpyHostToDevice, ctx->stream));
-  uint64_t *recs = nullptr, nt = 0, total = 0;
-  KMI_TRY(dbg_parse(ctx, &g->cfg, (const uint8_t *)d_bytes, n_bytes, true, &recs, &nt));   // (an empty share still enters the collectives)
+  void *d_send, *d_recv;
+  uint64_t total = 0;
   KMI_TRY(ws_get(ctx, WS_DIST_A, ((size_t)nt + 64) * rw * sizeof(uint64_t), &d_send));
   std::vector<uint64_t> sc(p, 0), rc;
   if (nt) KMI_TRY(kmi_route_tuples_dev(ctx, &g->nodes->cfg, recs, (size_t)nt, (uint32_t)p, 1, (uint64_t *)d_send, sc.data()));
@@ -4951,6 +4943,21 @@ kmi_status kmi_dbg_build_dist_host(kmi_dbg *g, kmi_comm *comm, const uint8_t *by
   dbg_unitigs_drop(g);
   if (p > 1) g->dist_share = true;
   return dbg_insert(g, (const uint64_t *)d_recv, (size_t)total);
+}
+
+// build over ranks: parse the rank's share, group the node-form tuples by KeyToRank of the canonical k-mer, one all-to-all
+// (imxx::distribute inside de_bruijn_nodes_distributed::insert, de_bruijn_nodes_distributed.hpp:243-250), insert what arrives
+kmi_status kmi_dbg_build_dist_host(kmi_dbg *g, kmi_comm *comm, const uint8_t *bytes, size_t n_bytes) {
+  if (!g) return KMI_ERR_INVALID;
+  KMI_TRY(dist_check(g->nodes, comm));
+  kmi_ctx *ctx = g->ctx;
+  if (alone(ctx, comm)) return kmi_dbg_build_host(g, bytes, n_bytes);
+  if (n_bytes && !bytes) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
+  void *d_bytes;
+  KMI_TRY(stage_host(ctx, WS_INPUT, bytes, n_bytes, 64, &d_bytes));
+  uint64_t *recs = nullptr, nt = 0;
+  KMI_TRY(dbg_parse(ctx, &g->cfg, (const uint8_t *)d_bytes, n_bytes, true, &recs, &nt));   // (an empty share still enters the collectives)
+  return dbg_route_exchange_insert(g, comm, recs, nt);
 }
 
 // find() of the node map over ranks: query keys to the ranks that own their canonical k-mer (the node map's KeyToRank), every
@@ -4961,43 +4968,26 @@ kmi_status kmi_dbg_find_dist_host(kmi_dbg *g, kmi_comm *comm, const uint64_t *qu
   KMI_TRY(dist_check(g->nodes, comm));
   kmi_ctx *ctx = g->ctx;
   const int p = kmi::comm_size(comm);
-  if (p == 1 && !ctx->force_dist) return kmi_dbg_find_host(g, queries, nq, out);
+  if (alone(ctx, comm)) return kmi_dbg_find_host(g, queries, nq, out);
   memset(out, 0, sizeof(*out));
   if (nq && !queries) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
   const uint32_t nw = g->shape.n_words;
   const size_t kb = nw * sizeof(uint64_t), vb = kDbgValueWords * sizeof(uint64_t);
-  void *d_in, *d_send, *d_q;
-  KMI_TRY(ws_get(ctx, WS_INPUT, (nq + 8) * kb, &d_in));
-  KMI_TRY(ws_get(ctx, WS_DIST_A, (nq + 8) * kb, &d_send));
-  if (nq) KMI_HIP(ctx, hipMemcpyAsync(d_in, queries, nq * kb, hipMemcpyHostToDevice, ctx->stream));
-  std::vector<uint64_t> sc(p, 0), rc;
-  KMI_TRY(kmi_route_dev(ctx, &g->nodes->cfg, (const uint64_t *)d_in, nq, (uint32_t)p, (uint64_t *)d_send, sc.data()));
+  void *d_q;
+  std::vector<uint64_t> rc;
   uint64_t total = 0;
-  KMI_TRY(dist_exchange(comm, d_send, sc.data(), kb, WS_DIST_B, &d_q, rc, &total));
+  KMI_TRY(keys_to_owners(g->nodes, comm, queries, nq, false, &d_q, rc, &total));
   void *d_rk, *d_rv;
   KMI_TRY(ws_get(ctx, WS_DIST_C, (total + 8) * kb, &d_rk));
   KMI_TRY(ws_get(ctx, WS_DIST_D, (total + 8) * vb, &d_rv));
-  std::vector<uint64_t> back(p, 0), got;
+  std::vector<uint64_t> back(p, 0);
   uint64_t off = 0, pos = 0;
   for (int s = 0; s < p; ++s) {
     uint64_t n = 0;
     if (rc[s]) KMI_TRY(dbg_find(g, (const uint64_t *)d_q + off * nw, (size_t)rc[s], (uint64_t *)d_rk + pos * nw, (uint64_t *)d_rv + pos * kDbgValueWords, &n));
     back[s] = n; off += rc[s]; pos += n;
   }
-  void *d_ak, *d_av;
-  uint64_t n_mine = 0, n_mine2 = 0;
-  KMI_TRY(dist_exchange(comm, d_rk, back.data(), kb, WS_DIST_A, &d_ak, got, &n_mine));
-  KMI_TRY(dist_exchange(comm, d_rv, back.data(), vb, WS_DIST_B, &d_av, got, &n_mine2));
-  out->n = n_mine;
-  out->keys = (uint64_t *)malloc((n_mine ? n_mine : 1) * kb);
-  out->values = (uint64_t *)malloc((n_mine ? n_mine : 1) * vb);
-  if (!out->keys || !out->values) return set_err(ctx, KMI_ERR_NOMEM, "host malloc failed");
-  if (n_mine) {
-    KMI_HIP(ctx, hipMemcpyAsync(out->keys, d_ak, n_mine * kb, hipMemcpyDeviceToHost, ctx->stream));
-    KMI_HIP(ctx, hipMemcpyAsync(out->values, d_av, n_mine * vb, hipMemcpyDeviceToHost, ctx->stream));
-  }
-  KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return KMI_OK;
+  return answers_to_askers(comm, d_rk, d_rv, back, kb, vb, out);
 }
 
 // build_posix / build_mmap(filename) of the engine with comm.size() > 1: the rank passes the bytes it read of the FASTQ file (its
@@ -5009,19 +4999,10 @@ kmi_status kmi_dbg_build_range_dist_host(kmi_dbg *g, kmi_comm *comm, const uint8
   kmi_ctx *ctx = g->ctx;
   *need_more = 0;
   if (n_bytes && !bytes) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  if (nominal_bytes > n_bytes) nominal_bytes = n_bytes;
-  uint64_t pos[2] = {0, nominal_bytes}, cut[2] = {0, n_bytes};
-  if (n_bytes) {
-    KMI_HIP(ctx, hipSetDevice(ctx->device));
-    void *d_bytes;
-    KMI_TRY(ws_get(ctx, WS_INPUT2, n_bytes + 64, &d_bytes));
-    KMI_HIP(ctx, hipMemcpyAsync(d_bytes, bytes, n_bytes, hipMemcpyHostToDevice, ctx->stream));
-    KMI_TRY(kmi_fastq_find_records_dev(ctx, (const uint8_t *)d_bytes, n_bytes, buffer_offset == 0, pos, 2, cut));
-    if (nominal_bytes >= n_bytes) cut[1] = n_bytes;
-  }
-  if (cut[1] >= n_bytes && !reaches_eof && n_bytes) { *need_more = 1; return KMI_OK; }
-  if (cut[0] >= n_bytes && !reaches_eof && n_bytes && buffer_offset != 0) { *need_more = 1; return KMI_OK; }
-  if (cut[1] < cut[0]) cut[1] = cut[0];
+  void *d_bytes;   // (only the cut is made from this copy: the build stages the host bytes of the cut range itself)
+  uint64_t cut[2] = {0, 0};
+  if (n_bytes) KMI_TRY(fastq_range_cut(ctx, WS_INPUT2, bytes, n_bytes, buffer_offset, nominal_bytes, reaches_eof, &d_bytes, cut, need_more));
+  if (*need_more) return KMI_OK;
   return kmi_dbg_build_dist_host(g, comm, bytes + cut[0], (size_t)(cut[1] - cut[0]));
 }
 
@@ -5038,10 +5019,8 @@ kmi_status kmi_dbg_build_fasta_range_dist_host(kmi_dbg *g, kmi_comm *comm, const
   if (g->cfg.seq_format != KMI_FMT_FASTA) return set_err(ctx, KMI_ERR_INVALID, "not a FASTA graph (kmi_dbg_set_seq_format)");
   if ((n_bytes && !bytes) || nominal_bytes > n_bytes) return set_err(ctx, KMI_ERR_INVALID, "bad buffer");
   KMI_HIP(ctx, hipSetDevice(ctx->device));
-  const int p = kmi::comm_size(comm);
   void *d_bytes;
-  KMI_TRY(ws_get(ctx, WS_INPUT, n_bytes + 64, &d_bytes));
-  if (n_bytes) KMI_HIP(ctx, hipMemcpyAsync(d_bytes, bytes, n_bytes, hipMemcpyHostToDevice, ctx->stream));
+  KMI_TRY(stage_host(ctx, WS_INPUT, bytes, n_bytes, 64, &d_bytes));
   kmi_fasta_partition part; uint64_t end = 0; int carry = -1;
   KMI_TRY(fasta_range_partition(ctx, comm, g->shape.k, bytes, (const uint8_t *)d_bytes, n_bytes, buffer_offset, nominal_bytes, reaches_eof,
                                 prev_byte, need_more, &part, &end, &carry));
@@ -5054,17 +5033,8 @@ kmi_status kmi_dbg_build_fasta_range_dist_host(kmi_dbg *g, kmi_comm *comm, const
   (void)kmi_ctx_set_fasta_partition(ctx, nullptr);
   KMI_TRY(stp);
   dbg_unitigs_drop(g);
-  if (p == 1 && !ctx->force_dist) return dbg_insert(g, recs, (size_t)nt);   // (one rank: every node is its own)
-  const uint32_t rw = g->shape.n_words + 1u;
-  void *d_send, *d_recv;
-  uint64_t total = 0;
-  KMI_TRY(ws_get(ctx, WS_DIST_A, ((size_t)nt + 64) * rw * sizeof(uint64_t), &d_send));
-  std::vector<uint64_t> sc(p, 0), rc;
-  if (nt) KMI_TRY(kmi_route_tuples_dev(ctx, &g->nodes->cfg, recs, (size_t)nt, (uint32_t)p, 1, (uint64_t *)d_send, sc.data()));
-  KMI_TRY(dist_exchange(comm, d_send, sc.data(), rw * sizeof(uint64_t), WS_DIST_B, &d_recv, rc, &total));
-  dbg_unitigs_drop(g);
-  if (p > 1) g->dist_share = true;
-  return dbg_insert(g, (const uint64_t *)d_recv, (size_t)total);
+  if (alone(ctx, comm)) return dbg_insert(g, recs, (size_t)nt);   // (one rank: every node is its own)
+  return dbg_route_exchange_insert(g, comm, recs, nt);
 }
 
 // erase(): the nodes of the query keys (either strand) leave the map
@@ -5076,8 +5046,8 @@ kmi_status kmi_dbg_erase_host(kmi_dbg *g, const uint64_t *queries, size_t nq, ui
   if (!queries) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
   KMI_HIP(ctx, hipSetDevice(ctx->device));
   void *dq;
-  KMI_TRY(ws_get(ctx, WS_INPUT, (nq + 8) * g->shape.n_words * sizeof(uint64_t), &dq));
-  KMI_HIP(ctx, hipMemcpyAsync(dq, queries, nq * g->shape.n_words * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
+  const size_t kb = g->shape.n_words * sizeof(uint64_t);
+  KMI_TRY(stage_host(ctx, WS_INPUT, queries, nq * kb, 8 * kb, &dq));
   dbg_unitigs_drop(g);
   return dbg_erase(g, (const uint64_t *)dq, nq, n_erased);
 }
@@ -5087,19 +5057,13 @@ kmi_status kmi_dbg_erase_dist_host(kmi_dbg *g, kmi_comm *comm, const uint64_t *q
   if (!g) return KMI_ERR_INVALID;
   KMI_TRY(dist_check(g->nodes, comm));
   kmi_ctx *ctx = g->ctx;
-  const int p = kmi::comm_size(comm);
-  if (p == 1 && !ctx->force_dist) return kmi_dbg_erase_host(g, queries, nq, n_erased_local);
+  if (alone(ctx, comm)) return kmi_dbg_erase_host(g, queries, nq, n_erased_local);
   if (n_erased_local) *n_erased_local = 0;
   if (nq && !queries) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  const size_t kb = g->shape.n_words * sizeof(uint64_t);
-  void *d_in, *d_send, *d_q;
-  KMI_TRY(ws_get(ctx, WS_INPUT, (nq + 8) * kb, &d_in));
-  KMI_TRY(ws_get(ctx, WS_DIST_A, (nq + 8) * kb, &d_send));
-  if (nq) KMI_HIP(ctx, hipMemcpyAsync(d_in, queries, nq * kb, hipMemcpyHostToDevice, ctx->stream));
-  std::vector<uint64_t> sc(p, 0), rc;
-  KMI_TRY(kmi_route_dev(ctx, &g->nodes->cfg, (const uint64_t *)d_in, nq, (uint32_t)p, (uint64_t *)d_send, sc.data()));
+  void *d_q;
+  std::vector<uint64_t> rc;
   uint64_t total = 0;
-  KMI_TRY(dist_exchange(comm, d_send, sc.data(), kb, WS_DIST_B, &d_q, rc, &total));
+  KMI_TRY(keys_to_owners(g->nodes, comm, queries, nq, false, &d_q, rc, &total));
   dbg_unitigs_drop(g);
   return dbg_erase(g, (const uint64_t *)d_q, (size_t)total, n_erased_local);
 }
@@ -5139,7 +5103,7 @@ kmi_status kmi_dbg_compact_dist_host(kmi_dbg *g, kmi_comm *comm, uint32_t min_ed
   KMI_TRY(dist_check(g->nodes, comm));
   kmi_ctx *ctx = g->ctx;
   uint64_t totals[2] = {0, 0};
-  if (kmi::comm_size(comm) == 1 && !ctx->force_dist) {
+  if (alone(ctx, comm)) {
     KMI_TRY(dbg_compact(g, min_edge_count));
     totals[0] = g->n_unitigs; totals[1] = g->n_unitig_bases;
   } else KMI_TRY(kmi::dbg_compact_dist(g, comm, min_edge_count, totals));
@@ -5242,55 +5206,40 @@ kmi_status kmi_route_owner_dev(kmi_ctx *ctx, const kmi_config *cfg, const uint64
 }
 
 // ---- update() with a device-side updater (kmi_update.h)
-kmi_status kmi_index_update_pairs_dev(kmi_index *idx, const uint64_t *records_dev, size_t n, uint32_t op, uint64_t *n_updated) {
+static kmi_status update_pairs_entry(kmi_index *idx, const uint64_t *records, size_t n, bool on_device, uint32_t op, uint64_t *n_updated) {
   if (!idx || !n_updated) return KMI_ERR_INVALID;
   kmi_ctx *ctx = idx->ctx;
   *n_updated = 0;
   if (idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "update() is a member of the counting maps");
   if (op > KMI_UPDATE_ASSIGN) return set_err(ctx, KMI_ERR_INVALID, "unknown updater");
+  if (!on_device) {
+    if (n == 0) return KMI_OK;
+    if (!records) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
+  }
   KMI_HIP(ctx, hipSetDevice(ctx->device));
   if (n == 0) return KMI_OK;
   void *dr;   // (the caller's buffer stays as it is)
   const size_t bytes = n * (idx->shape.n_words + 1) * sizeof(uint64_t);
   KMI_TRY(ws_get(ctx, WS_INPUT2, bytes + 64, &dr));
-  KMI_HIP(ctx, hipMemcpyAsync(dr, records_dev, bytes, hipMemcpyDeviceToDevice, ctx->stream));
+  KMI_HIP(ctx, hipMemcpyAsync(dr, records, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
   return index_update_pairs(idx, (uint64_t *)dr, n, (int)op, n_updated);
 }
-
+kmi_status kmi_index_update_pairs_dev(kmi_index *idx, const uint64_t *records_dev, size_t n, uint32_t op, uint64_t *n_updated) {
+  return update_pairs_entry(idx, records_dev, n, true, op, n_updated);
+}
 kmi_status kmi_index_update_pairs_host(kmi_index *idx, const uint64_t *records, size_t n, uint32_t op, uint64_t *n_updated) {
-  if (!idx || !n_updated) return KMI_ERR_INVALID;
-  kmi_ctx *ctx = idx->ctx;
-  *n_updated = 0;
-  if (idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "update() is a member of the counting maps");
-  if (op > KMI_UPDATE_ASSIGN) return set_err(ctx, KMI_ERR_INVALID, "unknown updater");
-  if (n == 0) return KMI_OK;
-  if (!records) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  void *dr;
-  const size_t bytes = n * (idx->shape.n_words + 1) * sizeof(uint64_t);
-  KMI_TRY(ws_get(ctx, WS_INPUT2, bytes + 64, &dr));
-  KMI_HIP(ctx, hipMemcpyAsync(dr, records, bytes, hipMemcpyHostToDevice, ctx->stream));
-  return index_update_pairs(idx, (uint64_t *)dr, n, (int)op, n_updated);
+  return update_pairs_entry(idx, records, n, false, op, n_updated);
 }
 
 // ---- queries in the caller's order (kmi_lookup.h)
-kmi_status kmi_index_lookup_dev(kmi_index *idx, const uint64_t *queries_dev, size_t nq, uint32_t *counts_dev) {
-  if (!idx) return KMI_ERR_INVALID;
-  kmi_ctx *ctx = idx->ctx;
-  if (idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "lookup() is a member of the count index");
-  if (nq == 0) return KMI_OK;
-  if (!queries_dev || !counts_dev) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  return index_lookup(idx, queries_dev, nq, counts_dev);
-}
-
-kmi_status kmi_index_lookup_host(kmi_index *idx, const uint64_t *queries, size_t nq, uint32_t *counts) {
+static kmi_status lookup_entry(kmi_index *idx, const uint64_t *queries, size_t nq, uint32_t *counts, bool on_device) {
   if (!idx) return KMI_ERR_INVALID;
   kmi_ctx *ctx = idx->ctx;
   if (idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "lookup() is a member of the count index");
   if (nq == 0) return KMI_OK;
   if (!queries || !counts) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
   KMI_HIP(ctx, hipSetDevice(ctx->device));
+  if (on_device) return index_lookup(idx, queries, nq, counts);
   void *dq, *dc;
   KMI_TRY(ws_get(ctx, WS_INPUT, nq * idx->shape.n_words * sizeof(uint64_t), &dq));
   KMI_TRY(ws_get(ctx, WS_OUTPUT, nq * sizeof(uint32_t), &dc));
@@ -5299,6 +5248,12 @@ kmi_status kmi_index_lookup_host(kmi_index *idx, const uint64_t *queries, size_t
   KMI_HIP(ctx, hipMemcpyAsync(counts, dc, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
   KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return KMI_OK;
+}
+kmi_status kmi_index_lookup_dev(kmi_index *idx, const uint64_t *queries_dev, size_t nq, uint32_t *counts_dev) {
+  return lookup_entry(idx, queries_dev, nq, counts_dev, true);
+}
+kmi_status kmi_index_lookup_host(kmi_index *idx, const uint64_t *queries, size_t nq, uint32_t *counts) {
+  return lookup_entry(idx, queries, nq, counts, false);
 }
 
 static kmi_status profile_reads_entry(kmi_index *idx, const uint8_t *bytes, size_t n_bytes, bool on_device, uint32_t solid_threshold,
@@ -5324,20 +5279,21 @@ kmi_status kmi_index_profile_reads_host(kmi_index *idx, const uint8_t *bytes, si
 }
 
 // ---- the position indexes in the caller's order (kmi_locate.h)
-kmi_status kmi_index_locate_dev(kmi_index *idx, const uint64_t *queries_dev, size_t nq, uint32_t max_occ, uint32_t *occ_dev, uint64_t *offsets_dev,
-                                uint64_t *values_dev, size_t capacity, uint64_t *n_hits) {
-  if (!idx || !n_hits) return KMI_ERR_INVALID;
+// what a locate over device buffers left, to the caller's host buffers; st = its status (occ and offsets are complete when only the
+// capacity was short)
+static kmi_status locate_download(kmi_index *idx, kmi_status st, size_t nq, uint32_t *occ, const void *dc, uint64_t *offsets, const void *dof,
+                                  uint64_t *values, const void *dv, size_t capacity, const uint64_t *n_hits) {
   kmi_ctx *ctx = idx->ctx;
-  *n_hits = 0;
-  if (!idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "locate() is a member of the position indexes");
-  if (max_occ == 0) return set_err(ctx, KMI_ERR_INVALID, "max_occ is at least 1");
-  if (!offsets_dev || (nq && (!queries_dev || !occ_dev)) || (!values_dev && capacity)) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  return index_locate(idx, queries_dev, nq, max_occ, occ_dev, offsets_dev, values_dev, capacity, n_hits);
+  if (st != KMI_OK && !(st == KMI_ERR_OVERFLOW && *n_hits > capacity)) return st;
+  if (nq) KMI_HIP(ctx, hipMemcpyAsync(occ, dc, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
+  KMI_HIP(ctx, hipMemcpyAsync(offsets, dof, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (st == KMI_OK && values && *n_hits)
+    KMI_HIP(ctx, hipMemcpyAsync(values, dv, *n_hits * idx->val_words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
+  KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
+  return st;
 }
-
-kmi_status kmi_index_locate_host(kmi_index *idx, const uint64_t *queries, size_t nq, uint32_t max_occ, uint32_t *occ, uint64_t *offsets,
-                                 uint64_t *values, size_t capacity, uint64_t *n_hits) {
+static kmi_status locate_entry(kmi_index *idx, const uint64_t *queries, size_t nq, bool on_device, uint32_t max_occ, uint32_t *occ, uint64_t *offsets,
+                               uint64_t *values, size_t capacity, uint64_t *n_hits) {
   if (!idx || !n_hits) return KMI_ERR_INVALID;
   kmi_ctx *ctx = idx->ctx;
   *n_hits = 0;
@@ -5345,6 +5301,7 @@ kmi_status kmi_index_locate_host(kmi_index *idx, const uint64_t *queries, size_t
   if (max_occ == 0) return set_err(ctx, KMI_ERR_INVALID, "max_occ is at least 1");
   if (!offsets || (nq && (!queries || !occ)) || (!values && capacity)) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
   KMI_HIP(ctx, hipSetDevice(ctx->device));
+  if (on_device) return index_locate(idx, queries, nq, max_occ, occ, offsets, values, capacity, n_hits);
   void *dq, *dc, *dof, *dv = nullptr;
   const size_t q_bytes = nq * idx->shape.n_words * sizeof(uint64_t), v_bytes = capacity * idx->val_words * sizeof(uint64_t);
   KMI_TRY(ws_get(ctx, WS_INPUT, q_bytes, &dq));
@@ -5353,14 +5310,15 @@ kmi_status kmi_index_locate_host(kmi_index *idx, const uint64_t *queries, size_t
   if (values) KMI_TRY(ws_get(ctx, WS_OUTPUT2, v_bytes, &dv));
   if (nq) KMI_HIP(ctx, hipMemcpyAsync(dq, queries, q_bytes, hipMemcpyHostToDevice, ctx->stream));
   const kmi_status st = index_locate(idx, (const uint64_t *)dq, nq, max_occ, (uint32_t *)dc, (uint64_t *)dof, (uint64_t *)dv, capacity, n_hits);
-  if (st != KMI_OK && !(st == KMI_ERR_OVERFLOW && *n_hits > capacity)) return st;
-  // (occ and offsets are complete when only the capacity was short)
-  if (nq) KMI_HIP(ctx, hipMemcpyAsync(occ, dc, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  KMI_HIP(ctx, hipMemcpyAsync(offsets, dof, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (st == KMI_OK && values && *n_hits)
-    KMI_HIP(ctx, hipMemcpyAsync(values, dv, *n_hits * idx->val_words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-  KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return st;
+  return locate_download(idx, st, nq, occ, dc, offsets, dof, values, dv, capacity, n_hits);
+}
+kmi_status kmi_index_locate_dev(kmi_index *idx, const uint64_t *queries_dev, size_t nq, uint32_t max_occ, uint32_t *occ_dev, uint64_t *offsets_dev,
+                                uint64_t *values_dev, size_t capacity, uint64_t *n_hits) {
+  return locate_entry(idx, queries_dev, nq, true, max_occ, occ_dev, offsets_dev, values_dev, capacity, n_hits);
+}
+kmi_status kmi_index_locate_host(kmi_index *idx, const uint64_t *queries, size_t nq, uint32_t max_occ, uint32_t *occ, uint64_t *offsets,
+                                 uint64_t *values, size_t capacity, uint64_t *n_hits) {
+  return locate_entry(idx, queries, nq, false, max_occ, occ, offsets, values, capacity, n_hits);
 }
 
 static kmi_status seed_reads_entry(kmi_index *idx, const uint8_t *bytes, size_t n_bytes, bool on_device, uint32_t max_occ, kmi_read_seeds *rows,
@@ -5398,20 +5356,13 @@ static kmi_status query_dist_check(kmi_index *idx, kmi_comm *comm, bool position
     return set_err(ctx, KMI_ERR_INVALID, "%s(): the index is distributed over another number of owner ranks than the communicator has", what);
   return KMI_OK;
 }
-static bool query_dist_alone(kmi_index *idx, kmi_comm *comm) { return kmi::comm_size(comm) == 1 && !idx->ctx->force_dist; }
 
-kmi_status kmi_index_lookup_dist_dev(kmi_index *idx, kmi_comm *comm, const uint64_t *queries_dev, size_t nq, uint32_t *counts_dev) {
-  KMI_TRY(query_dist_check(idx, comm, false, "lookup"));
-  if (nq && (!queries_dev || !counts_dev)) return set_err(idx->ctx, KMI_ERR_INVALID, "null buffer");
-  if (query_dist_alone(idx, comm)) return kmi_index_lookup_dev(idx, queries_dev, nq, counts_dev);
-  return index_lookup_dist(idx, comm, queries_dev, nq, counts_dev);
-}
-
-kmi_status kmi_index_lookup_dist_host(kmi_index *idx, kmi_comm *comm, const uint64_t *queries, size_t nq, uint32_t *counts) {
+static kmi_status lookup_dist_entry(kmi_index *idx, kmi_comm *comm, const uint64_t *queries, size_t nq, uint32_t *counts, bool on_device) {
   KMI_TRY(query_dist_check(idx, comm, false, "lookup"));
   kmi_ctx *ctx = idx->ctx;
   if (nq && (!queries || !counts)) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  if (query_dist_alone(idx, comm)) return kmi_index_lookup_host(idx, queries, nq, counts);
+  if (alone(ctx, comm)) return lookup_entry(idx, queries, nq, counts, on_device);
+  if (on_device) return index_lookup_dist(idx, comm, queries, nq, counts);
   void *dq = nullptr, *dc = nullptr;
   const size_t q_bytes = nq * idx->shape.n_words * sizeof(uint64_t);
   const kmi_status staged = [&]() -> kmi_status {
@@ -5426,6 +5377,12 @@ kmi_status kmi_index_lookup_dist_host(kmi_index *idx, kmi_comm *comm, const uint
   KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   return KMI_OK;
 }
+kmi_status kmi_index_lookup_dist_dev(kmi_index *idx, kmi_comm *comm, const uint64_t *queries_dev, size_t nq, uint32_t *counts_dev) {
+  return lookup_dist_entry(idx, comm, queries_dev, nq, counts_dev, true);
+}
+kmi_status kmi_index_lookup_dist_host(kmi_index *idx, kmi_comm *comm, const uint64_t *queries, size_t nq, uint32_t *counts) {
+  return lookup_dist_entry(idx, comm, queries, nq, counts, false);
+}
 
 static kmi_status profile_reads_dist_entry(kmi_index *idx, kmi_comm *comm, const uint8_t *bytes, size_t n_bytes, bool on_device, uint32_t solid_threshold,
                                            kmi_read_profile *out, size_t capacity, uint64_t *n_reads) {
@@ -5436,7 +5393,7 @@ static kmi_status profile_reads_dist_entry(kmi_index *idx, kmi_comm *comm, const
   if (idx->cfg.seq_format != KMI_FMT_FASTQ) return set_err(ctx, KMI_ERR_INVALID, "profile_reads() reads FASTQ");
   if (solid_threshold == 0) return set_err(ctx, KMI_ERR_INVALID, "solid_threshold is at least 1");
   if ((n_bytes && !bytes) || (!out && capacity)) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  if (query_dist_alone(idx, comm))
+  if (alone(idx->ctx, comm))
     return on_device ? kmi_index_profile_reads_dev(idx, bytes, n_bytes, solid_threshold, out, capacity, n_reads)
                      : kmi_index_profile_reads_host(idx, bytes, n_bytes, solid_threshold, out, capacity, n_reads);
   return index_profile_reads_dist(idx, comm, bytes, n_bytes, on_device, solid_threshold, out, capacity, n_reads);
@@ -5450,27 +5407,16 @@ kmi_status kmi_index_profile_reads_dist_host(kmi_index *idx, kmi_comm *comm, con
   return profile_reads_dist_entry(idx, comm, bytes, n_bytes, false, solid_threshold, out, capacity, n_reads);
 }
 
-kmi_status kmi_index_locate_dist_dev(kmi_index *idx, kmi_comm *comm, const uint64_t *queries_dev, size_t nq, uint32_t max_occ, uint32_t *occ_dev,
-                                     uint64_t *offsets_dev, uint64_t *values_dev, size_t capacity, uint64_t *n_hits) {
-  if (!n_hits) return KMI_ERR_INVALID;
-  *n_hits = 0;
-  KMI_TRY(query_dist_check(idx, comm, true, "locate"));
-  kmi_ctx *ctx = idx->ctx;
-  if (max_occ == 0) return set_err(ctx, KMI_ERR_INVALID, "max_occ is at least 1");
-  if (!offsets_dev || (nq && (!queries_dev || !occ_dev)) || (!values_dev && capacity)) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  if (query_dist_alone(idx, comm)) return kmi_index_locate_dev(idx, queries_dev, nq, max_occ, occ_dev, offsets_dev, values_dev, capacity, n_hits);
-  return index_locate_dist(idx, comm, queries_dev, nq, max_occ, occ_dev, offsets_dev, values_dev, capacity, n_hits);
-}
-
-kmi_status kmi_index_locate_dist_host(kmi_index *idx, kmi_comm *comm, const uint64_t *queries, size_t nq, uint32_t max_occ, uint32_t *occ,
-                                      uint64_t *offsets, uint64_t *values, size_t capacity, uint64_t *n_hits) {
+static kmi_status locate_dist_entry(kmi_index *idx, kmi_comm *comm, const uint64_t *queries, size_t nq, bool on_device, uint32_t max_occ, uint32_t *occ,
+                                    uint64_t *offsets, uint64_t *values, size_t capacity, uint64_t *n_hits) {
   if (!n_hits) return KMI_ERR_INVALID;
   *n_hits = 0;
   KMI_TRY(query_dist_check(idx, comm, true, "locate"));
   kmi_ctx *ctx = idx->ctx;
   if (max_occ == 0) return set_err(ctx, KMI_ERR_INVALID, "max_occ is at least 1");
   if (!offsets || (nq && (!queries || !occ)) || (!values && capacity)) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  if (query_dist_alone(idx, comm)) return kmi_index_locate_host(idx, queries, nq, max_occ, occ, offsets, values, capacity, n_hits);
+  if (alone(ctx, comm)) return locate_entry(idx, queries, nq, on_device, max_occ, occ, offsets, values, capacity, n_hits);
+  if (on_device) return index_locate_dist(idx, comm, queries, nq, max_occ, occ, offsets, values, capacity, n_hits);
   void *dq = nullptr, *dc = nullptr, *dof = nullptr, *dv = nullptr;
   const size_t q_bytes = nq * idx->shape.n_words * sizeof(uint64_t), v_bytes = capacity * idx->val_words * sizeof(uint64_t);
   const kmi_status staged = [&]() -> kmi_status {
@@ -5483,14 +5429,15 @@ kmi_status kmi_index_locate_dist_host(kmi_index *idx, kmi_comm *comm, const uint
   }();
   if (staged != KMI_OK) { uint64_t more = 0, want = 0; return qd_agree(comm, staged, &more, &want); }   // (the peers are told in their first all-reduce)
   const kmi_status st = index_locate_dist(idx, comm, (const uint64_t *)dq, nq, max_occ, (uint32_t *)dc, (uint64_t *)dof, (uint64_t *)dv, capacity, n_hits);
-  if (st != KMI_OK && !(st == KMI_ERR_OVERFLOW && *n_hits > capacity)) return st;
-  // (occ and offsets are complete when only the capacity was short)
-  if (nq) KMI_HIP(ctx, hipMemcpyAsync(occ, dc, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  KMI_HIP(ctx, hipMemcpyAsync(offsets, dof, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (st == KMI_OK && values && *n_hits)
-    KMI_HIP(ctx, hipMemcpyAsync(values, dv, *n_hits * idx->val_words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-  KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return st;
+  return locate_download(idx, st, nq, occ, dc, offsets, dof, values, dv, capacity, n_hits);
+}
+kmi_status kmi_index_locate_dist_dev(kmi_index *idx, kmi_comm *comm, const uint64_t *queries_dev, size_t nq, uint32_t max_occ, uint32_t *occ_dev,
+                                     uint64_t *offsets_dev, uint64_t *values_dev, size_t capacity, uint64_t *n_hits) {
+  return locate_dist_entry(idx, comm, queries_dev, nq, true, max_occ, occ_dev, offsets_dev, values_dev, capacity, n_hits);
+}
+kmi_status kmi_index_locate_dist_host(kmi_index *idx, kmi_comm *comm, const uint64_t *queries, size_t nq, uint32_t max_occ, uint32_t *occ,
+                                      uint64_t *offsets, uint64_t *values, size_t capacity, uint64_t *n_hits) {
+  return locate_dist_entry(idx, comm, queries, nq, false, max_occ, occ, offsets, values, capacity, n_hits);
 }
 
 static kmi_status seed_reads_dist_entry(kmi_index *idx, kmi_comm *comm, const uint8_t *bytes, size_t n_bytes, bool on_device, uint32_t max_occ,
@@ -5503,7 +5450,7 @@ static kmi_status seed_reads_dist_entry(kmi_index *idx, kmi_comm *comm, const ui
   if (max_occ == 0) return set_err(ctx, KMI_ERR_INVALID, "max_occ is at least 1");
   if ((n_bytes && !bytes) || (!rows && cap_reads) || ((!occ || !offsets) && cap_kmers) || (!values && cap_hits))
     return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  if (query_dist_alone(idx, comm))
+  if (alone(idx->ctx, comm))
     return seed_reads_entry(idx, bytes, n_bytes, on_device, max_occ, rows, cap_reads, occ, offsets, cap_kmers, values, cap_hits, n_reads, n_kmers, n_hits);
   return index_seed_reads_dist(idx, comm, bytes, n_bytes, on_device, max_occ, rows, cap_reads, occ, offsets, cap_kmers, values, cap_hits, n_reads,
                                n_kmers, n_hits);
@@ -5625,7 +5572,7 @@ kmi_status kmi_dbg_prune_edges_dist_host(kmi_dbg *g, kmi_comm *comm, uint32_t mi
   KMI_TRY(dist_check(g->nodes, comm));
   uint64_t sl[8], stt[8];
   kmi_status st;
-  if (kmi::comm_size(comm) == 1 && !g->ctx->force_dist) {
+  if (alone(g->ctx, comm)) {
     st = kmi::dbg_prune(g, min_edge_count, sl);
     memcpy(stt, sl, sizeof(sl));
   } else st = kmi::dbg_prune_dist(g, comm, min_edge_count, sl, stt);
