@@ -44,8 +44,7 @@ constexpr int kSlotBits = 32 - kFineBits;    // low 17 bits pick the LDS slot
 constexpr int kPartThreads = 1024;           // K1/K2/P2 workgroup size
 constexpr int kPartGroups = 512;             // K1/K2 workgroups (two per CU)
 constexpr int kFineParts = 2;                // P2 workgroups per coarse bucket; part h = K2 groups [h*256, (h+1)*256)
-// workgroups of the list-driven histogram and scatter passes (they own the same tiles)
-// workgroups of the fused passes (E1 and E2 cut the scan tiles the same way)
+// workgroups of the fused build's list-driven histogram (E1) and coarse scatter (E2) passes: both cut the scan tiles the same way
 template <int NW> constexpr int fused_groups() { return kPartGroups; }
 constexpr int kListGroups = 2048;            // workgroups of the window-list pass (small LDS footprint: eight per CU)
 constexpr int kLoadBatch = 8;                // independent key loads kept in flight per thread
@@ -4341,1287 +4340,10 @@ static kmi_status dist_state(kmi_index *idx, kmi_comm *comm, uint64_t *holders, 
 
 #include "kmi_query_dist.h"
 
-// The count index over ranks through exchanged super-k-mer records, CHUNKED: the rank's share is cut into record-aligned chunks;
-// the records of chunk c travel on the communicator's stream while the front end of chunk c + 1 runs on the context's; the
-// counts of a chunk ride with the verdict ("this rank could not produce it": then every rank sends that chunk as k-mers to the
-// same owners afterwards) and with the sender's largest message. What arrived is consumed in one go.
-static kmi_status build_dist_superkmer(kmi_index *idx, uint32_t w, kmi_comm *comm, const uint8_t *d_bytes, size_t n_bytes, uint64_t file_offset) {
-  kmi_ctx *ctx = idx->ctx;
-  const int p = kmi::comm_size(comm);
-  const uint32_t lp = 31u - (uint32_t)__builtin_clz((uint32_t)p);
-  const uint32_t nch = (idx->cfg.seq_format == KMI_FMT_FASTQ) ? ctx->dist_chunks : 1u;
-  std::vector<uint64_t> cuts(nch + 1, 0);
-  if (n_bytes) {
-    if (nch > 1) KMI_TRY(kmi_fastq_partition_dev(ctx, d_bytes, n_bytes, nch, cuts.data()));
-    else cuts[1] = n_bytes;
-  }
-  // the receive pool: every rank's bytes are known after one all-reduce; a rank receives about a p-th of all records
-  uint64_t all_bytes = n_bytes;
-  KMI_TRY(kmi::comm_allreduce_sum(comm, &all_bytes));
-  uint64_t pool_cap = (uint64_t)((double)all_bytes / p * 0.06 * 1.3 * ctx->dist_pool_pct / 100.0) + ctx->dist_pool_slack;
-  void *pv;
-  KMI_TRY(ws_get(ctx, WS_DIST_B, pool_cap * 16, &pv));
-  uint64_t *pool = (uint64_t *)pv;
-  uint64_t pool_pos = 0;
-  bool pool_in_b = true;
-  uint64_t *sendbuf[2] = {nullptr, nullptr};
-  size_t send_cap[2] = {0, 0};
-  std::vector<uint32_t> failed;
-  std::vector<uint64_t> sc(p), rc(p);
-  const uint32_t lp_before = idx->owner_lp;
-  idx->owner_lp = lp;   // (every rank is here: the route was agreed on; an error below puts the old value back)
-  // A rank that fails on its own -- a parse or length verdict of its front end, a workspace it cannot get -- still enters the
-  // chunk's count exchange and says so there (count = kHardError), so that every rank leaves this function with an error instead
-  // of waiting in a send / receive for a peer that has already returned.
-  constexpr uint64_t kNotProduced = ~0ull, kHardError = ~0ull - 1ull;
-  kmi_status st_local = KMI_OK;
-  bool peer_error = false;
-  for (uint32_t c = 0; c < nch && st_local == KMI_OK && !peer_error; ++c) {
-    const size_t cb = (size_t)(cuts[c + 1] - cuts[c]);
-    const int sb = (int)(c & 1u);
-    int produced = 0;
-    auto produce_chunk = [&]() -> kmi_status {
-      const size_t want = (size_t)((double)cb * 0.06) + 8192;
-      if (c >= 2) KMI_TRY(kmi::comm_exchange_wait(comm));   // the buffer's previous message has left (the transfer before the last is done)
-      if (send_cap[sb] < want) { KMI_TRY(ws_get(ctx, sb ? WS_DIST_C : WS_DIST_A, want * 16, &pv)); sendbuf[sb] = (uint64_t *)pv; send_cap[sb] = want; }
-      const uint64_t *recs = nullptr;
-      uint64_t nrec = 0;
-      const uint8_t *src = d_bytes + cuts[c];   // (any address: the one-pass front end loads unaligned; the general one aligns its input itself)
-      if (ctx->sk_dbg == 9 && comm_rank_of(comm) == 1 && c == 1) return set_err(ctx, KMI_ERR_PARSE, "test knob KMI_SK_DBG=9: rank 1 fails on its second chunk");
-      KMI_TRY(sk_produce(idx, w, src, cb, (uint32_t)p, &recs, &nrec, sc.data(), &produced, sendbuf[sb], send_cap[sb]));
-      if (produced && nrec && recs != sendbuf[sb]) {   // more records than the buffer was sized for: a larger one, and a copy out of the workspace
-        KMI_TRY(kmi::comm_exchange_wait(comm));
-        KMI_TRY(ws_get(ctx, sb ? WS_DIST_C : WS_DIST_A, (nrec + 64) * 16, &pv)); sendbuf[sb] = (uint64_t *)pv; send_cap[sb] = nrec + 64;
-        KMI_HIP(ctx, hipMemcpyAsync(sendbuf[sb], recs, nrec * 16, hipMemcpyDeviceToDevice, ctx->stream));
-      }
-      return KMI_OK;
-    };
-    st_local = produce_chunk();
-    uint64_t mine = 0, largest = 0;
-    for (int r = 0; r < p; ++r) mine = std::max(mine, sc[r] * 16);
-    std::vector<uint64_t> tell(sc);
-    if (st_local != KMI_OK) { for (int r = 0; r < p; ++r) tell[r] = kHardError; mine = 0; }
-    else if (!produced) for (int r = 0; r < p; ++r) tell[r] = kNotProduced;
-    {
-      const kmi_status st_x = kmi::comm_all_to_all_counts2(comm, tell.data(), mine, rc.data(), &largest);
-      if (st_x != KMI_OK) { idx->owner_lp = lp_before; return st_local != KMI_OK ? st_local : st_x; }   // (the exchange itself failed: nothing more to agree on)
-    }
-    for (int r = 0; r < p; ++r) peer_error = peer_error || rc[r] == kHardError;
-    if (st_local != KMI_OK || peer_error) break;
-    bool all_ok = produced != 0;
-    for (int r = 0; r < p; ++r) all_ok = all_ok && rc[r] != kNotProduced;
-    if (!all_ok) { failed.push_back(c); continue; }
-    uint64_t n_in = 0;
-    for (int r = 0; r < p; ++r) n_in += rc[r];
-    // (from here to the payload exchange only allocation can fail: a rank that cannot hold what it is sent has no way left to say so)
-    if (pool_pos + n_in > pool_cap) {   // the estimate was short (a very uneven input): a pool twice the need, what arrived so far moves over
-      KMI_TRY(kmi::comm_exchange_wait(comm));
-      const uint64_t ncap = 2 * (pool_pos + n_in) + ctx->dist_pool_slack;
-      ++ctx->dist_pool_regrows;
-      KMI_TRY(ws_get(ctx, pool_in_b ? WS_DIST_D : WS_DIST_B, ncap * 16, &pv));
-      if (pool_pos) KMI_HIP(ctx, hipMemcpyAsync(pv, pool, pool_pos * 16, hipMemcpyDeviceToDevice, ctx->stream));
-      pool = (uint64_t *)pv; pool_cap = ncap; pool_in_b = !pool_in_b;
-    }
-    KMI_TRY(kmi::comm_all_to_all_v_async(comm, sendbuf[sb], sc.data(), pool + 2 * pool_pos, rc.data(), 16, largest));
-    pool_pos += n_in;
-  }
-  KMI_TRY(kmi::comm_exchange_join(comm));
-  if (st_local != KMI_OK || peer_error) {
-    // what arrived before the error is dropped: the index is as it was (the transfers queued so far have been joined)
-    (void)hipStreamSynchronize(ctx->stream);
-    idx->owner_lp = lp_before;
-    if (st_local != KMI_OK) return st_local;
-    return set_err(ctx, KMI_ERR_PEER, "the build over ranks was given up: another rank reported an error in its share of the input");
-  }
-  {
-    kmi_status st_c = pool_pos ? sk_consume(idx, w, pool, pool_pos, (uint32_t)p) : KMI_OK;
-    // chunks some rank could not produce as records follow as k-mers, collectively: first agree that every rank is still there
-    if (!failed.empty()) st_c = dist_agree(comm, st_c);
-    if (st_c != KMI_OK) { if (!pool_pos || !idx->n_entries) idx->owner_lp = lp_before; return st_c; }
-  }
-  idx->owner_lp = lp;
-  // chunks some rank could not produce as records: their k-mers, routed to the same owners (collective: every rank has the same list)
-  for (uint32_t c : failed) {
-    const size_t cb = (size_t)(cuts[c + 1] - cuts[c]);
-    const uint32_t nw = idx->shape.n_words;
-    uint64_t nt = 0, ns = 0, total = 0;
-    void *d_keys = nullptr, *d_send = nullptr, *d_recv = nullptr;
-    auto route_chunk = [&]() -> kmi_status {
-      const uint8_t *src = d_bytes + cuts[c];
-      if (cb) { KMI_TRY(align_input(ctx, &src, cb)); KMI_TRY(extract_count(ctx, &idx->cfg, src, cb, &nt, &ns)); }
-      KMI_TRY(ws_get(ctx, WS_OUTPUT, (nt + 64) * nw * sizeof(uint64_t), &d_keys));
-      KMI_TRY(ws_get(ctx, WS_DIST_A, (nt + 64) * nw * sizeof(uint64_t), &d_send));
-      send_cap[0] = 0;
-      for (int r = 0; r < p; ++r) sc[r] = 0;
-      if (nt) {
-        KMI_TRY(extract_run(ctx, &idx->cfg, src, cb, file_offset + cuts[c], (uint64_t *)d_keys, nullptr, (size_t)nt, true, true, &nt, &ns));
-        KMI_TRY(kmi_route_owner_dev(ctx, &idx->cfg, (const uint64_t *)d_keys, (size_t)nt, (uint32_t)p, (uint64_t *)d_send, sc.data()));
-      }
-      return KMI_OK;
-    };
-    KMI_TRY(dist_agree(comm, route_chunk()));
-    std::vector<uint64_t> rcv;
-    KMI_TRY(dist_exchange(comm, d_send, sc.data(), nw * sizeof(uint64_t), WS_DIST_D, &d_recv, rcv, &total));
-    KMI_TRY(index_insert(idx, (const uint64_t *)d_recv, (size_t)total, false));
-    idx->owner_lp = lp;
-  }
-  return KMI_OK;
-}
-
-extern "C" {
-
-kmi_status kmi_index_build_dist_dev(kmi_index *idx, kmi_comm *comm, const uint8_t *d_bytes, size_t n_bytes, uint64_t file_offset) {
-  KMI_TRY(dist_check(idx, comm));
-  kmi_ctx *ctx = idx->ctx;
-  const int p = kmi::comm_size(comm);
-  if (alone(ctx, comm)) return kmi_index_build_dev(idx, d_bytes, n_bytes, file_offset);
-  if (n_bytes && !d_bytes) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  const uint32_t nw = idx->shape.n_words, vw = idx->val_words, rw = nw + vw;
-  void *d_send = nullptr, *d_recv;
-  std::vector<uint64_t> sc(p, 0), rc;
-  uint64_t nt = 0, ns = 0, total = 0;
-  if (vw == 0) {
-    // the route follows from state every rank has agreed on (never from one rank's own entry count: a rank with an empty share
-    // would otherwise take another branch than its peers, and the branches issue different collectives)
-    uint64_t holders = 0, owner_p = 0, owner_any = 0;
-    KMI_TRY(dist_state(idx, comm, &holders, &owner_p, &owner_any));
-    if (owner_any && owner_any != (uint64_t)p && holders)
-      return set_err(ctx, KMI_ERR_INVALID, "the ranks disagree on how this index is distributed (some by minimizer owner, some not)");
-    const uint32_t skw = sk_width_of(idx);
-    const bool by_owner = owner_any != 0 && holders != 0;                 // the entries are already distributed by minimizer owner
-    if (skw && sk_rank_count((uint32_t)p) && (holders == 0 || owner_p == (uint64_t)p)) {
-      if (holders == 0) idx->owner_lp = 0;
-      return build_dist_superkmer(idx, skw, comm, d_bytes, n_bytes, file_offset);
-    }
-    KMI_TRY(align_input(ctx, &d_bytes, n_bytes));   // (the scan's 16-byte loads: a range build hands in its buffer + the first record's offset)
-    if (n_bytes) KMI_TRY(extract_count(ctx, &idx->cfg, d_bytes, n_bytes, &nt, &ns));   // (an empty share still enters the collectives)
-    KMI_TRY(ws_get(ctx, WS_DIST_A, (nt + 64) * nw * sizeof(uint64_t), &d_send));
-    if (by_owner) {
-      // k-mers into an index that is distributed by minimizer owner go to those owners
-      void *d_keys;
-      KMI_TRY(ws_get(ctx, WS_OUTPUT, (nt + 64) * nw * sizeof(uint64_t), &d_keys));
-      if (nt) {
-        KMI_TRY(extract_run(ctx, &idx->cfg, d_bytes, n_bytes, file_offset, (uint64_t *)d_keys, nullptr, (size_t)nt, true, true, &nt, &ns));
-        KMI_TRY(kmi_route_owner_dev(ctx, &idx->cfg, (const uint64_t *)d_keys, (size_t)nt, (uint32_t)p, (uint64_t *)d_send, sc.data()));
-      }
-    } else if (nt && idx->cfg.seq_format == KMI_FMT_FASTQ) {
-      // read_file + the bucketing half of imxx::distribute, fused: the tuple array in file order never exists
-      KMI_TRY(kmi_extract_route_dev(ctx, &idx->cfg, d_bytes, n_bytes, (uint32_t)p, (uint64_t *)d_send, (size_t)nt, &nt, &ns, sc.data()));
-    } else if (nt) {
-      void *d_keys;
-      KMI_TRY(ws_get(ctx, WS_OUTPUT, (nt + 64) * nw * sizeof(uint64_t), &d_keys));
-      KMI_TRY(extract_run(ctx, &idx->cfg, d_bytes, n_bytes, file_offset, (uint64_t *)d_keys, nullptr, (size_t)nt, true, true, &nt, &ns));
-      KMI_TRY(kmi_route_dev(ctx, &idx->cfg, (const uint64_t *)d_keys, (size_t)nt, (uint32_t)p, (uint64_t *)d_send, sc.data()));
-    }
-    KMI_TRY(dist_exchange(comm, d_send, sc.data(), nw * sizeof(uint64_t), WS_DIST_B, &d_recv, rc, &total));
-    return index_insert(idx, (const uint64_t *)d_recv, (size_t)total, false);
-  }
-  KMI_TRY(align_input(ctx, &d_bytes, n_bytes));
-  if (n_bytes) KMI_TRY(extract_count(ctx, &idx->cfg, d_bytes, n_bytes, &nt, &ns));
-  if (vw == 2 && idx->cfg.seq_format != KMI_FMT_FASTQ)
-    return set_err(ctx, KMI_ERR_INVALID, "a position + quality index over ranks is built from FASTQ partitions");
-  KMI_TRY(ws_get(ctx, WS_DIST_A, (nt + 64) * rw * sizeof(uint64_t), &d_send));
-  if (nt)
-    KMI_TRY(kmi_extract_route_records_dev(ctx, &idx->cfg, d_bytes, n_bytes, file_offset, (uint32_t)p, (uint64_t *)d_send, (size_t)nt + 64,
-                                          &nt, &ns, sc.data()));
-  KMI_TRY(dist_exchange(comm, d_send, sc.data(), rw * sizeof(uint64_t), WS_DIST_B, &d_recv, rc, &total));
-  return index_insert_records(idx, (const uint64_t *)d_recv, (size_t)total, true);
-}
-
-kmi_status kmi_index_build_range_dist_host(kmi_index *idx, kmi_comm *comm, const uint8_t *bytes, size_t n_bytes, uint64_t buffer_offset,
-                                           uint64_t nominal_bytes, int reaches_eof, int *need_more) {
-  KMI_TRY(dist_check(idx, comm));
-  kmi_ctx *ctx = idx->ctx;
-  if (!need_more) return KMI_ERR_INVALID;
-  *need_more = 0;
-  if (n_bytes && !bytes) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  if (idx->cfg.seq_format != KMI_FMT_FASTQ) return set_err(ctx, KMI_ERR_INVALID, "a byte range of a file is cut at FASTQ record starts here (a FASTA partition comes with kmi_ctx_set_fasta_partition)");
-  void *d_bytes;
-  uint64_t cut[2];
-  KMI_TRY(fastq_range_cut(ctx, WS_INPUT, bytes, n_bytes, buffer_offset, nominal_bytes, reaches_eof, &d_bytes, cut, need_more));
-  if (*need_more) return KMI_OK;
-  return kmi_index_build_dist_dev(idx, comm, (const uint8_t *)d_bytes + cut[0], (size_t)(cut[1] - cut[0]), buffer_offset + cut[0]);
-}
-
-kmi_status kmi_index_build_fasta_file_dist_host(kmi_index *idx, kmi_comm *comm, const uint8_t *bytes, size_t n_bytes) {
-  // every rank holds the WHOLE FASTA file; the block bookkeeping of an equal split over the ranks (where each block's valid range
-  // begins, the machine state and the record count there: file.hpp:1436-1610 + fasta_loader.hpp:202-470) is computed on the device
-  // from the whole buffer, every rank keeps its own block and enters the collective build with it
-  KMI_TRY(dist_check(idx, comm));
-  kmi_ctx *ctx = idx->ctx;
-  if (idx->cfg.seq_format != KMI_FMT_FASTA) return set_err(ctx, KMI_ERR_INVALID, "not a FASTA index");
-  if (n_bytes && !bytes) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  const uint32_t p = (uint32_t)kmi::comm_size(comm), r = (uint32_t)kmi::comm_rank(comm);
-  void *d_bytes;
-  KMI_TRY(stage_host(ctx, WS_INPUT, bytes, n_bytes, 64, &d_bytes));
-  std::vector<uint64_t> be(2 * (size_t)p);
-  std::vector<kmi_fasta_partition> parts(p);
-  KMI_TRY(kmi_fasta_partition_dev(ctx, (const uint8_t *)d_bytes, n_bytes, p, idx->shape.k, be.data(), parts.data()));
-  KMI_TRY(kmi_ctx_set_fasta_partition(ctx, &parts[r]));
-  const kmi_status st = kmi_index_build_dist_dev(idx, comm, (const uint8_t *)d_bytes + be[2 * r], (size_t)(be[2 * r + 1] - be[2 * r]), be[2 * r]);
-  (void)kmi_ctx_set_fasta_partition(ctx, nullptr);
-  return st;
-}
-
-// FASTA over ranks by BYTE RANGE (file.hpp:1436-1610, fasta_loader.hpp:202-470): the rank brings only its block of an equal split of
-// the file plus look-ahead, and what it cannot know from its own bytes -- the kind of line its first byte sits on, the records that
-// start before it, whether the file opens with a header -- comes from the other ranks' block summaries (kmi_fasta_block_summary_dev:
-// the line-kind machine over a block as a transfer function), gathered once and composed left to right. bytes = file bytes
-// [buffer_offset, buffer_offset + n_bytes), the first nominal_bytes of them the rank's block; prev_byte = the file byte before the
-// buffer (-1 at the file start); *need_more = 1: the `behind` sequence characters behind the block (the last windows' overlap: k - 1
-// for k-mers, k for de Bruijn tuples, whose last window also needs its right neighbour) do not end inside the look-ahead -- nothing
-// collective has happened, the caller reads further and calls again.
-// the bookkeeping of a block: *need_more (nothing collective has happened then), or the partition record and where the block's
-// windows end inside the buffer. d_bytes = the buffer on the device (already in flight on the context's stream). carry_out
-// (optional): the raw byte of the last sequence character before the block in the same record, -1 when there is none (a record
-// starts in between, or the block opens the file) -- the in-edge of the block's first window, from the blocks' left carries
-// composed right to left.
-static kmi_status fasta_range_partition(kmi_ctx *ctx, kmi_comm *comm, uint32_t behind, const uint8_t *bytes, const uint8_t *d_bytes, size_t n_bytes,
-                                        uint64_t buffer_offset, uint64_t nominal_bytes, int reaches_eof, int prev_byte, int *need_more,
-                                        kmi_fasta_partition *part_out, uint64_t *end_out, int *carry_out = nullptr) {
-  const uint32_t p = (uint32_t)kmi::comm_size(comm), r = (uint32_t)kmi::comm_rank(comm);
-  const bool first_ls = buffer_offset == 0 || prev_byte == (int)'\n';
-  constexpr size_t NWD = 11;   // out6, the file's first byte, the block's length, the left carry per incoming state
-  uint64_t mine[NWD] = {0, 0, 1, 0, 2, 0, 0, 0, 0, 0, 0};
-  KMI_TRY(kmi::fasta_block_summary(ctx, d_bytes, (size_t)nominal_bytes, first_ls, mine, mine + 8));
-  mine[6] = (buffer_offset == 0 && n_bytes) ? bytes[0] : 0;   // (rank 0: the file's first byte decides init_parser's index shift)
-  mine[7] = nominal_bytes;
-  // where the overlap ends: the behind-th sequence character at or behind the block's end, for every state the machine may be in there
-  auto step = [](uint32_t &state, uint8_t c) {
-    if (c == '>' || c == ';') state = KMI_FA_HEADER;
-    else state = (state == KMI_FA_OUTSIDE) ? (uint32_t)KMI_FA_OUTSIDE : (uint32_t)KMI_FA_SEQUENCE;
-  };
-  uint64_t end_for[3] = {nominal_bytes, nominal_bytes, nominal_bytes};
-  for (uint32_t st0 = 0; st0 < 3; ++st0) {
-    if (behind == 0 || nominal_bytes >= n_bytes) { end_for[st0] = nominal_bytes < n_bytes ? nominal_bytes : n_bytes; continue; }
-    uint32_t st = st0, need = behind;
-    uint64_t i = nominal_bytes;
-    for (; i < n_bytes && need; ++i) {
-      const uint8_t c = bytes[i];
-      const bool ls = i == 0 ? first_ls : bytes[i - 1] == '\n';
-      if (ls) step(st, c);
-      if (st == KMI_FA_SEQUENCE && c != '\n' && c != '\r') --need;
-    }
-    if (need && !reaches_eof) { *need_more = 1; return KMI_OK; }
-    end_for[st0] = need ? n_bytes : i;
-  }
-  if (behind > 0 && nominal_bytes >= n_bytes && !reaches_eof && p > 1 && r + 1 < p) { *need_more = 1; return KMI_OK; }   // (no look-ahead at all behind a block that is not the file's last)
-  // ---- collective from here on
-  std::vector<uint64_t> all((size_t)p * NWD);
-  KMI_TRY(kmi::comm_allgather_words(comm, mine, NWD, all.data()));
-  uint32_t st = KMI_FA_OUTSIDE; uint64_t ev = 0;
-  std::vector<uint32_t> st_in(r + 1);   // the state every block before this one is entered in
-  for (uint32_t q = 0; q < r; ++q) { const uint64_t *t = &all[(size_t)q * NWD]; st_in[q] = st; ev += t[2 * st + 1]; st = (uint32_t)t[2 * st]; }
-  if (carry_out) {
-    *carry_out = -1;
-    for (uint32_t q = r; q-- > 0;) {   // the nearest block to the left that holds a sequence character or a record start decides
-      const uint64_t c = all[(size_t)q * NWD + 8 + st_in[q]];
-      if (c == kmi::KMI_FA_CARRY_PASS) continue;
-      if (c & kmi::KMI_FA_CARRY_BYTE) *carry_out = (int)(c & 0xFFu);
-      break;
-    }
-  }
-  uint64_t first = 0;
-  for (uint32_t q = 0; q < p; ++q) if (all[(size_t)q * NWD + 7]) { first = all[(size_t)q * NWD + 6]; break; }   // the first non-empty block opens the file
-  kmi_fasta_partition part; memset(&part, 0, sizeof(part));
-  part.valid_bytes = nominal_bytes;
-  part.start_state = buffer_offset == 0 ? (uint32_t)KMI_FA_OUTSIDE : st;
-  part.at_line_start = first_ls ? 1u : 0u;
-  part.records_before = ev;
-  part.index_shift = (first == '>' || first == ';') ? 0u : 1u;
-  const uint32_t st_end = (uint32_t)mine[2 * part.start_state];   // the machine's state behind the block
-  const uint64_t end = end_for[st_end] < nominal_bytes ? nominal_bytes : end_for[st_end];
-  *part_out = part;
-  *end_out = end < n_bytes ? end : n_bytes;
-  return KMI_OK;
-}
-
-kmi_status kmi_index_build_fasta_range_dist_host(kmi_index *idx, kmi_comm *comm, const uint8_t *bytes, size_t n_bytes, uint64_t buffer_offset,
-                                                 uint64_t nominal_bytes, int reaches_eof, int prev_byte, int *need_more) {
-  KMI_TRY(dist_check(idx, comm));
-  kmi_ctx *ctx = idx->ctx;
-  if (!need_more) return KMI_ERR_INVALID;
-  *need_more = 0;
-  if (idx->cfg.seq_format != KMI_FMT_FASTA) return set_err(ctx, KMI_ERR_INVALID, "not a FASTA index");
-  if ((n_bytes && !bytes) || nominal_bytes > n_bytes) return set_err(ctx, KMI_ERR_INVALID, "bad buffer");
-  void *d_bytes;
-  KMI_TRY(stage_host(ctx, WS_INPUT, bytes, n_bytes, 64, &d_bytes));
-  kmi_fasta_partition part; uint64_t end = 0;
-  KMI_TRY(fasta_range_partition(ctx, comm, idx->shape.k - 1u, bytes, (const uint8_t *)d_bytes, n_bytes, buffer_offset, nominal_bytes, reaches_eof,
-                                prev_byte, need_more, &part, &end));
-  if (*need_more) return KMI_OK;
-  KMI_TRY(kmi_ctx_set_fasta_partition(ctx, &part));
-  const kmi_status stb = kmi_index_build_dist_dev(idx, comm, (const uint8_t *)d_bytes, (size_t)end, buffer_offset);
-  (void)kmi_ctx_set_fasta_partition(ctx, nullptr);
-  return stb;
-}
-
-// read_file_* of a FASTA file on one rank of several, by byte range (kmer_file_helper.hpp:550-633 over FASTALoader's partitions,
-// fasta_loader.hpp:202-470): the same bookkeeping, then the block's tuples to the host. Collective over comm (one small gather).
-kmi_status kmi_extract_fasta_range_dist_host(kmi_ctx *ctx, const kmi_config *cfg, kmi_comm *comm, const uint8_t *bytes, size_t n_bytes,
-                                             uint64_t buffer_offset, uint64_t nominal_bytes, int reaches_eof, int prev_byte, int *need_more,
-                                             kmi_tuples *out) {
-  if (!ctx || !cfg || !comm || !out || !need_more) return KMI_ERR_INVALID;
-  memset(out, 0, sizeof(*out));
-  *need_more = 0;
-  if (cfg->seq_format != KMI_FMT_FASTA) return set_err(ctx, KMI_ERR_INVALID, "not FASTA");
-  if ((n_bytes && !bytes) || nominal_bytes > n_bytes) return set_err(ctx, KMI_ERR_INVALID, "bad buffer");
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  void *d_bytes;
-  KMI_TRY(stage_host(ctx, WS_INPUT2, bytes, n_bytes, 64, &d_bytes));
-  kmi_fasta_partition part; uint64_t end = 0;
-  KMI_TRY(fasta_range_partition(ctx, comm, cfg->k - 1u, bytes, (const uint8_t *)d_bytes, n_bytes, buffer_offset, nominal_bytes, reaches_eof,
-                                prev_byte, need_more, &part, &end));
-  if (*need_more || end == 0) return KMI_OK;
-  KMI_TRY(kmi_ctx_set_fasta_partition(ctx, &part));
-  const kmi_status st = kmi_extract_host(ctx, cfg, bytes, (size_t)end, buffer_offset, out);
-  (void)kmi_ctx_set_fasta_partition(ctx, nullptr);
-  return st;
-}
-
-kmi_status kmi_index_build_dist_host(kmi_index *idx, kmi_comm *comm, const uint8_t *bytes, size_t n_bytes, uint64_t file_offset) {
-  KMI_TRY(dist_check(idx, comm));
-  kmi_ctx *ctx = idx->ctx;
-  if (alone(ctx, comm)) return kmi_index_build_host(idx, bytes, n_bytes, file_offset);
-  if (n_bytes && !bytes) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  void *d_bytes;
-  KMI_TRY(stage_host(ctx, WS_INPUT, bytes, n_bytes, 64, &d_bytes));
-  return kmi_index_build_dist_dev(idx, comm, (const uint8_t *)d_bytes, n_bytes, file_offset);
-}
-
-static kmi_status query_dist_host(kmi_index *idx, kmi_comm *comm, int mode, const uint64_t *queries, size_t nq, kmi_results *out, uint64_t *n_erased) {
-  KMI_TRY(dist_check(idx, comm));
-  kmi_ctx *ctx = idx->ctx;
-  const int p = kmi::comm_size(comm);
-  if (alone(ctx, comm)) return query_host(idx, mode, queries, nq, out, n_erased);
-  if (out) memset(out, 0, sizeof(*out));
-  if (n_erased) *n_erased = 0;
-  if (nq && !queries) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  const uint32_t nw = idx->shape.n_words, ow = idx->val_words ? idx->val_words : 1u;
-  const size_t kb = nw * sizeof(uint64_t), vb = ow * sizeof(uint64_t);
-  void *d_q;
-  std::vector<uint64_t> rc;
-  uint64_t total = 0;
-  KMI_TRY(keys_to_owners(idx, comm, queries, nq, idx->owner_lp != 0, &d_q, rc, &total));
-  if (mode == Q_ERASE) {
-    uint64_t n = 0;
-    if (total) KMI_TRY(index_query(idx, Q_ERASE, (const uint64_t *)d_q, (size_t)total, nullptr, nullptr, 0, &n));
-    if (n_erased) *n_erased = n;
-    return KMI_OK;
-  }
-  // every source rank's keys are answered on their own (a key two ranks ask about is answered to both). The answers of a multimap
-  // find are sized by a count of the hits per source (a bound by the entries of the index, per source, is p times the index)
-  const bool mm_find = idx->val_words > 0 && mode == Q_FIND;
-  std::vector<uint64_t> back(p, 0);
-  uint64_t bound = 0, off = 0;
-  for (int s = 0; s < p; ++s) {
-    if (mm_find) {
-      if (rc[s]) KMI_TRY(index_query(idx, mode, (const uint64_t *)d_q + off * nw, (size_t)rc[s], nullptr, nullptr, 0, &back[s], nullptr, nullptr, true));
-      bound += back[s];
-    } else bound += query_result_bound(idx, mode, (size_t)rc[s]);
-    off += rc[s];
-  }
-  void *d_rk, *d_rv;
-  KMI_TRY(ws_get(ctx, WS_DIST_C, (bound + 8) * kb, &d_rk));
-  KMI_TRY(ws_get(ctx, WS_DIST_D, (bound + 8) * vb, &d_rv));
-  uint64_t pos = 0;
-  off = 0;
-  for (int s = 0; s < p; ++s) {
-    uint64_t n = 0;
-    if (rc[s] && (!mm_find || back[s]))
-      KMI_TRY(index_query(idx, mode, (const uint64_t *)d_q + off * nw, (size_t)rc[s], (uint64_t *)d_rk + pos * nw, (uint64_t *)d_rv + pos * ow,
-                          mm_find ? back[s] : query_result_bound(idx, mode, (size_t)rc[s]), &n));
-    back[s] = n; off += rc[s]; pos += n;
-  }
-  return answers_to_askers(comm, d_rk, d_rv, back, kb, vb, out);
-}
-
-kmi_status kmi_index_count_dist_host(kmi_index *idx, kmi_comm *comm, const uint64_t *queries, size_t nq, kmi_results *out) {
-  if (!out) return KMI_ERR_INVALID;
-  return query_dist_host(idx, comm, Q_COUNT, queries, nq, out, nullptr);
-}
-kmi_status kmi_index_find_dist_host(kmi_index *idx, kmi_comm *comm, const uint64_t *queries, size_t nq, kmi_results *out) {
-  if (!out) return KMI_ERR_INVALID;
-  return query_dist_host(idx, comm, Q_FIND, queries, nq, out, nullptr);
-}
-kmi_status kmi_index_erase_dist_host(kmi_index *idx, kmi_comm *comm, const uint64_t *queries, size_t nq, uint64_t *n_erased_local) {
-  return query_dist_host(idx, comm, Q_ERASE, queries, nq, nullptr, n_erased_local);
-}
-kmi_status kmi_index_size_dist(kmi_index *idx, kmi_comm *comm, uint64_t *n) {
-  if (!n) return KMI_ERR_INVALID;
-  KMI_TRY(dist_check(idx, comm));
-  *n = idx->n_entries;
-  return kmi::comm_allreduce_sum(comm, n);
-}
-
-// ---- de Bruijn graph nodes (kmi_debruijn.h)
-kmi_status kmi_dbg_create(kmi_ctx *ctx, const kmi_config *cfg, uint32_t node_kind, kmi_dbg **out) {
-  if (!ctx || !out) return KMI_ERR_INVALID;
-  KShape shape;
-  if (!valid_config(cfg, &shape)) return set_err(ctx, KMI_ERR_INVALID, "bad kmi_config");
-  if (node_kind > KMI_DBG_EDGE_EXISTS) return set_err(ctx, KMI_ERR_INVALID, "unknown node kind");
-  if (cfg->seq_filter != KMI_SEQ_ALL)
-    return set_err(ctx, KMI_ERR_INVALID, "de Bruijn nodes are built from every record of the input (no sequence filter), as the reference's engine is");
-  kmi_dbg *g = new kmi_dbg();
-  g->ctx = ctx; g->cfg = *cfg; g->shape = shape; g->node_kind = node_kind;
-  kmi_config c = *cfg;   // the node map proper: both strands of a k-mer are one node, kept under the smaller one
-  c.index_kind = KMI_INDEX_COUNT; c.strand = KMI_STRAND_CANONICAL; c.dist_trans = KMI_DIST_MODEL;
-  const kmi_status st = kmi_index_create(ctx, &c, &g->nodes);
-  if (st != KMI_OK) { delete g; return st; }
-  *out = g;
-  return KMI_OK;
-}
-
-// the SeqParser template argument of the engine's build_posix / build_mmap (FASTQParser or FASTAParser)
-kmi_status kmi_dbg_set_seq_format(kmi_dbg *g, uint32_t seq_format) {
-  if (!g) return KMI_ERR_INVALID;
-  if (seq_format > KMI_FMT_FASTA) return set_err(g->ctx, KMI_ERR_INVALID, "unknown sequence format");
-  g->cfg.seq_format = seq_format;
-  return KMI_OK;
-}
-
-kmi_status kmi_dbg_destroy(kmi_dbg *g) {
-  if (!g) return KMI_OK;
-  (void)hipSetDevice(g->ctx->device);
-  (void)hipStreamSynchronize(g->ctx->stream);
-  dbg_unitigs_drop(g);
-  if (g->edges) pool_free(g->ctx, g->edges, g->edges_bytes);
-  (void)kmi_index_destroy(g->nodes);
-  delete g;
-  return KMI_OK;
-}
-
-kmi_status kmi_dbg_clear(kmi_dbg *g) {
-  if (!g) return KMI_ERR_INVALID;
-  KMI_TRY(kmi_index_clear(g->nodes));
-  dbg_unitigs_drop(g);
-  if (g->edges) pool_free(g->ctx, g->edges, g->edges_bytes);
-  g->edges = nullptr; g->edges_bytes = 0;
-  g->dist_share = false;
-  return KMI_OK;
-}
-
-kmi_status kmi_dbg_local_size(kmi_dbg *g, uint64_t *n) {
-  if (!g || !n) return KMI_ERR_INVALID;
-  *n = g->nodes->n_entries;
-  return KMI_OK;
-}
-
-kmi_status kmi_dbg_parse_dev(kmi_ctx *ctx, const kmi_config *cfg, const uint8_t *bytes_dev, size_t n_bytes, uint64_t *out_records_dev,
-                             size_t out_capacity, uint64_t *n_tuples) {
-  if (!ctx || !n_tuples) return KMI_ERR_INVALID;
-  KShape shape;
-  if (!valid_config(cfg, &shape)) return set_err(ctx, KMI_ERR_INVALID, "bad kmi_config");
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  uint64_t *recs = nullptr;
-  KMI_TRY(dbg_parse(ctx, cfg, bytes_dev, n_bytes, false, &recs, n_tuples));
-  if (!out_records_dev) return KMI_OK;   // count only
-  if (*n_tuples > out_capacity) return set_err(ctx, KMI_ERR_OVERFLOW, "parse: output capacity too small");
-  if (*n_tuples) KMI_HIP(ctx, hipMemcpyAsync(out_records_dev, recs, (size_t)*n_tuples * (shape.n_words + 1) * sizeof(uint64_t), hipMemcpyDeviceToDevice, ctx->stream));
-  KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return KMI_OK;
-}
-
-kmi_status kmi_dbg_build_dev(kmi_dbg *g, const uint8_t *bytes_dev, size_t n_bytes) {
-  if (!g) return KMI_ERR_INVALID;
-  kmi_ctx *ctx = g->ctx;
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  if (n_bytes == 0) return KMI_OK;
-  dbg_unitigs_drop(g);
-  {   // an empty graph from clean FASTQ reads: through super-k-mer records (dbg_build_superkmer); else, and for what that declines, tuples
-    bool done = false;
-    KMI_TRY(dbg_build_superkmer(g, bytes_dev, n_bytes, &done));
-    if (done) return KMI_OK;
-  }
-  uint64_t *recs = nullptr, nt = 0;
-  KMI_TRY(dbg_parse(ctx, &g->cfg, bytes_dev, n_bytes, true, &recs, &nt));
-  return dbg_insert(g, recs, (size_t)nt);
-}
-
-kmi_status kmi_dbg_build_host(kmi_dbg *g, const uint8_t *bytes, size_t n_bytes) {
-  if (!g) return KMI_ERR_INVALID;
-  kmi_ctx *ctx = g->ctx;
-  if (n_bytes == 0) return KMI_OK;
-  if (!bytes) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  void *din;
-  KMI_TRY(stage_host(ctx, WS_INPUT, bytes, n_bytes, 64, &din));
-  return kmi_dbg_build_dev(g, (const uint8_t *)din, n_bytes);
-}
-
-// tuples as the parser emits them (any strand; value word = edge byte); they are rewritten in place into node form
-static kmi_status dbg_insert_tuples(kmi_dbg *g, uint64_t *recs_dev, size_t n) {
-  dbg_unitigs_drop(g);
-  KMI_TRY(dbg_edges(g->ctx, recs_dev, n, nullptr, 0, g->shape, false, true));
-  return dbg_insert(g, recs_dev, n);
-}
-
-static kmi_status dbg_insert_entry(kmi_dbg *g, const uint64_t *records, size_t n, bool on_device) {
-  if (!g) return KMI_ERR_INVALID;
-  kmi_ctx *ctx = g->ctx;
-  if (!on_device) {
-    if (n == 0) return KMI_OK;
-    if (!records) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  }
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  if (n == 0) return KMI_OK;
-  void *dr;   // (the caller's buffer stays as it is)
-  const size_t bytes = n * (g->shape.n_words + 1) * sizeof(uint64_t);
-  KMI_TRY(ws_get(ctx, WS_DBG_RECS, bytes + 64, &dr));
-  KMI_HIP(ctx, hipMemcpyAsync(dr, records, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
-  return dbg_insert_tuples(g, (uint64_t *)dr, n);
-}
-kmi_status kmi_dbg_insert_dev(kmi_dbg *g, const uint64_t *records_dev, size_t n) { return dbg_insert_entry(g, records_dev, n, true); }
-kmi_status kmi_dbg_insert_host(kmi_dbg *g, const uint64_t *records, size_t n) { return dbg_insert_entry(g, records, n, false); }
-
-kmi_status kmi_dbg_find_dev(kmi_dbg *g, const uint64_t *queries_dev, size_t nq, uint64_t *out_keys_dev, uint64_t *out_values_dev, uint64_t *n_out) {
-  if (!g || !n_out) return KMI_ERR_INVALID;
-  KMI_HIP(g->ctx, hipSetDevice(g->ctx->device));
-  return dbg_find(g, queries_dev, nq, out_keys_dev, out_values_dev, n_out);
-}
-
-kmi_status kmi_dbg_find_host(kmi_dbg *g, const uint64_t *queries, size_t nq, kmi_results *out) {
-  if (!g || !out) return KMI_ERR_INVALID;
-  kmi_ctx *ctx = g->ctx;
-  memset(out, 0, sizeof(*out));
-  if (nq == 0) return KMI_OK;
-  if (!queries) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  const uint32_t nw = g->shape.n_words;
-  void *dq, *dk, *dv;
-  KMI_TRY(ws_get(ctx, WS_INPUT, nq * nw * sizeof(uint64_t), &dq));
-  KMI_TRY(ws_get(ctx, WS_OUTPUT, nq * nw * sizeof(uint64_t), &dk));
-  KMI_TRY(ws_get(ctx, WS_OUTPUT2, nq * kDbgValueWords * sizeof(uint64_t), &dv));
-  KMI_HIP(ctx, hipMemcpyAsync(dq, queries, nq * nw * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-  uint64_t n = 0;
-  KMI_TRY(dbg_find(g, (const uint64_t *)dq, nq, (uint64_t *)dk, (uint64_t *)dv, &n));
-  return results_to_host(ctx, out, dk, dv, n, nw * sizeof(uint64_t), kDbgValueWords * sizeof(uint64_t));
-}
-
-kmi_status kmi_dbg_count_host(kmi_dbg *g, const uint64_t *queries, size_t nq, kmi_results *out) {
-  if (!g) return KMI_ERR_INVALID;
-  return kmi_index_count_host(g->nodes, queries, nq, out);
-}
-
-kmi_status kmi_dbg_export_host(kmi_dbg *g, uint64_t *keys, uint32_t *counts9, size_t capacity, uint64_t *n) {
-  if (!g || !n) return KMI_ERR_INVALID;
-  kmi_ctx *ctx = g->ctx;
-  *n = 0;
-  const uint64_t ne = g->nodes->n_entries;
-  if (ne == 0) return KMI_OK;
-  if (capacity < ne) return set_err(ctx, KMI_ERR_OVERFLOW, "export: capacity too small");
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  if (keys) KMI_HIP(ctx, hipMemcpyAsync(keys, g->nodes->keys, ne * g->shape.n_words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (counts9) {
-    std::vector<uint32_t> e(ne * 8), s(ne);
-    KMI_HIP(ctx, hipMemcpyAsync(e.data(), g->edges, ne * 8 * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    KMI_HIP(ctx, hipMemcpyAsync(s.data(), g->nodes->vals, ne * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-    KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-    const bool ex = g->node_kind == KMI_DBG_EDGE_EXISTS;
-    for (uint64_t i = 0; i < ne; ++i) {
-      for (int t = 0; t < 8; ++t) counts9[i * 9 + t] = ex ? (e[i * 8 + t] ? 1u : 0u) : e[i * 8 + t];
-      counts9[i * 9 + 8] = ex ? 0u : s[i];
-    }
-  }
-  KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  *n = ne;
-  return KMI_OK;
-}
-
-// the tail of the builds over ranks: nt node-form tuples grouped by KeyToRank of the canonical k-mer, one all-to-all, and what
-// arrives inserted (a rank without tuples still enters the exchange)
-static kmi_status dbg_route_exchange_insert(kmi_dbg *g, kmi_comm *comm, const uint64_t *recs, uint64_t nt) {
-  kmi_ctx *ctx = g->ctx;
-  const int p = kmi::comm_size(comm);
-  const uint32_t rw = g->shape.n_words + 1u;
-  void *d_send, *d_recv;
-  uint64_t total = 0;
-  KMI_TRY(ws_get(ctx, WS_DIST_A, ((size_t)nt + 64) * rw * sizeof(uint64_t), &d_send));
-  std::vector<uint64_t> sc(p, 0), rc;
-  if (nt) KMI_TRY(kmi_route_tuples_dev(ctx, &g->nodes->cfg, recs, (size_t)nt, (uint32_t)p, 1, (uint64_t *)d_send, sc.data()));
-  KMI_TRY(dist_exchange(comm, d_send, sc.data(), rw * sizeof(uint64_t), WS_DIST_B, &d_recv, rc, &total));
-  dbg_unitigs_drop(g);
-  if (p > 1) g->dist_share = true;
-  return dbg_insert(g, (const uint64_t *)d_recv, (size_t)total);
-}
-
-// build over ranks: parse the rank's share, group the node-form tuples by KeyToRank of the canonical k-mer, one all-to-all
-// (imxx::distribute inside de_bruijn_nodes_distributed::insert, de_bruijn_nodes_distributed.hpp:243-250), insert what arrives
-kmi_status kmi_dbg_build_dist_host(kmi_dbg *g, kmi_comm *comm, const uint8_t *bytes, size_t n_bytes) {
-  if (!g) return KMI_ERR_INVALID;
-  KMI_TRY(dist_check(g->nodes, comm));
-  kmi_ctx *ctx = g->ctx;
-  if (alone(ctx, comm)) return kmi_dbg_build_host(g, bytes, n_bytes);
-  if (n_bytes && !bytes) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  void *d_bytes;
-  KMI_TRY(stage_host(ctx, WS_INPUT, bytes, n_bytes, 64, &d_bytes));
-  uint64_t *recs = nullptr, nt = 0;
-  KMI_TRY(dbg_parse(ctx, &g->cfg, (const uint8_t *)d_bytes, n_bytes, true, &recs, &nt));   // (an empty share still enters the collectives)
-  return dbg_route_exchange_insert(g, comm, recs, nt);
-}
-
-// find() of the node map over ranks: query keys to the ranks that own their canonical k-mer (the node map's KeyToRank), every
-// source's keys answered on their own, one return exchange of (k-mer, node) -- distributed_unordered_map.hpp:564-687 as the
-// node map inherits it (de_bruijn_nodes_distributed.hpp:61)
-kmi_status kmi_dbg_find_dist_host(kmi_dbg *g, kmi_comm *comm, const uint64_t *queries, size_t nq, kmi_results *out) {
-  if (!g || !out) return KMI_ERR_INVALID;
-  KMI_TRY(dist_check(g->nodes, comm));
-  kmi_ctx *ctx = g->ctx;
-  const int p = kmi::comm_size(comm);
-  if (alone(ctx, comm)) return kmi_dbg_find_host(g, queries, nq, out);
-  memset(out, 0, sizeof(*out));
-  if (nq && !queries) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  const uint32_t nw = g->shape.n_words;
-  const size_t kb = nw * sizeof(uint64_t), vb = kDbgValueWords * sizeof(uint64_t);
-  void *d_q;
-  std::vector<uint64_t> rc;
-  uint64_t total = 0;
-  KMI_TRY(keys_to_owners(g->nodes, comm, queries, nq, false, &d_q, rc, &total));
-  void *d_rk, *d_rv;
-  KMI_TRY(ws_get(ctx, WS_DIST_C, (total + 8) * kb, &d_rk));
-  KMI_TRY(ws_get(ctx, WS_DIST_D, (total + 8) * vb, &d_rv));
-  std::vector<uint64_t> back(p, 0);
-  uint64_t off = 0, pos = 0;
-  for (int s = 0; s < p; ++s) {
-    uint64_t n = 0;
-    if (rc[s]) KMI_TRY(dbg_find(g, (const uint64_t *)d_q + off * nw, (size_t)rc[s], (uint64_t *)d_rk + pos * nw, (uint64_t *)d_rv + pos * kDbgValueWords, &n));
-    back[s] = n; off += rc[s]; pos += n;
-  }
-  return answers_to_askers(comm, d_rk, d_rv, back, kb, vb, out);
-}
-
-// build_posix / build_mmap(filename) of the engine with comm.size() > 1: the rank passes the bytes it read of the FASTQ file (its
-// nominal range + look-ahead), the partition is cut at record starts on the device (kmi_index_build_range_dist_host's rule)
-kmi_status kmi_dbg_build_range_dist_host(kmi_dbg *g, kmi_comm *comm, const uint8_t *bytes, size_t n_bytes, uint64_t buffer_offset,
-                                         uint64_t nominal_bytes, int reaches_eof, int *need_more) {
-  if (!g || !need_more) return KMI_ERR_INVALID;
-  KMI_TRY(dist_check(g->nodes, comm));
-  kmi_ctx *ctx = g->ctx;
-  *need_more = 0;
-  if (n_bytes && !bytes) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  void *d_bytes;   // (only the cut is made from this copy: the build stages the host bytes of the cut range itself)
-  uint64_t cut[2] = {0, 0};
-  if (n_bytes) KMI_TRY(fastq_range_cut(ctx, WS_INPUT2, bytes, n_bytes, buffer_offset, nominal_bytes, reaches_eof, &d_bytes, cut, need_more));
-  if (*need_more) return KMI_OK;
-  return kmi_dbg_build_dist_host(g, comm, bytes + cut[0], (size_t)(cut[1] - cut[0]));
-}
-
-// build over ranks from a FASTA file by BYTE RANGE (the engine's build_posix / build_mmap<FASTAParser> with comm.size() > 1): the
-// bookkeeping of kmi_index_build_fasta_range_dist_host, where the block's windows need k sequence characters behind it (the last
-// window's right neighbour) and its first window's left neighbour comes from the blocks before it (the left carries, in the same
-// gather); then the node-form tuples of the block are routed, exchanged once and inserted as kmi_dbg_build_dist_host does
-kmi_status kmi_dbg_build_fasta_range_dist_host(kmi_dbg *g, kmi_comm *comm, const uint8_t *bytes, size_t n_bytes, uint64_t buffer_offset,
-                                               uint64_t nominal_bytes, int reaches_eof, int prev_byte, int *need_more) {
-  if (!g || !need_more) return KMI_ERR_INVALID;
-  KMI_TRY(dist_check(g->nodes, comm));
-  kmi_ctx *ctx = g->ctx;
-  *need_more = 0;
-  if (g->cfg.seq_format != KMI_FMT_FASTA) return set_err(ctx, KMI_ERR_INVALID, "not a FASTA graph (kmi_dbg_set_seq_format)");
-  if ((n_bytes && !bytes) || nominal_bytes > n_bytes) return set_err(ctx, KMI_ERR_INVALID, "bad buffer");
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  void *d_bytes;
-  KMI_TRY(stage_host(ctx, WS_INPUT, bytes, n_bytes, 64, &d_bytes));
-  kmi_fasta_partition part; uint64_t end = 0; int carry = -1;
-  KMI_TRY(fasta_range_partition(ctx, comm, g->shape.k, bytes, (const uint8_t *)d_bytes, n_bytes, buffer_offset, nominal_bytes, reaches_eof,
-                                prev_byte, need_more, &part, &end, &carry));
-  if (*need_more) return KMI_OK;
-  uint64_t *recs = nullptr, nt = 0;
-  KMI_TRY(kmi_ctx_set_fasta_partition(ctx, &part));
-  ctx->fa_left_carry = carry;
-  const kmi_status stp = dbg_parse(ctx, &g->cfg, (const uint8_t *)d_bytes, (size_t)end, true, &recs, &nt);
-  ctx->fa_left_carry = -1;
-  (void)kmi_ctx_set_fasta_partition(ctx, nullptr);
-  KMI_TRY(stp);
-  dbg_unitigs_drop(g);
-  if (alone(ctx, comm)) return dbg_insert(g, recs, (size_t)nt);   // (one rank: every node is its own)
-  return dbg_route_exchange_insert(g, comm, recs, nt);
-}
-
-// erase(): the nodes of the query keys (either strand) leave the map
-kmi_status kmi_dbg_erase_host(kmi_dbg *g, const uint64_t *queries, size_t nq, uint64_t *n_erased) {
-  if (!g) return KMI_ERR_INVALID;
-  kmi_ctx *ctx = g->ctx;
-  if (n_erased) *n_erased = 0;
-  if (nq == 0) return KMI_OK;
-  if (!queries) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  void *dq;
-  const size_t kb = g->shape.n_words * sizeof(uint64_t);
-  KMI_TRY(stage_host(ctx, WS_INPUT, queries, nq * kb, 8 * kb, &dq));
-  dbg_unitigs_drop(g);
-  return dbg_erase(g, (const uint64_t *)dq, nq, n_erased);
-}
-
-// ... over ranks: the keys travel to the ranks that own them (*n_erased_local = nodes that left THIS rank's part)
-kmi_status kmi_dbg_erase_dist_host(kmi_dbg *g, kmi_comm *comm, const uint64_t *queries, size_t nq, uint64_t *n_erased_local) {
-  if (!g) return KMI_ERR_INVALID;
-  KMI_TRY(dist_check(g->nodes, comm));
-  kmi_ctx *ctx = g->ctx;
-  if (alone(ctx, comm)) return kmi_dbg_erase_host(g, queries, nq, n_erased_local);
-  if (n_erased_local) *n_erased_local = 0;
-  if (nq && !queries) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  void *d_q;
-  std::vector<uint64_t> rc;
-  uint64_t total = 0;
-  KMI_TRY(keys_to_owners(g->nodes, comm, queries, nq, false, &d_q, rc, &total));
-  dbg_unitigs_drop(g);
-  return dbg_erase(g, (const uint64_t *)d_q, (size_t)total, n_erased_local);
-}
-
-// count() over ranks: the node map's keys live in a count index, whose collective answers 1 per node held
-kmi_status kmi_dbg_count_dist_host(kmi_dbg *g, kmi_comm *comm, const uint64_t *queries, size_t nq, kmi_results *out) {
-  if (!g) return KMI_ERR_INVALID;
-  return kmi_index_count_dist_host(g->nodes, comm, queries, nq, out);
-}
-
-kmi_status kmi_dbg_size_dist(kmi_dbg *g, kmi_comm *comm, uint64_t *n) {
-  if (!g) return KMI_ERR_INVALID;
-  return kmi_index_size_dist(g->nodes, comm, n);
-}
-
-// unitigs (kmi_unitig.h): compaction on the device, the result kept in the graph until it changes
-kmi_status kmi_dbg_compact(kmi_dbg *g, uint32_t min_edge_count, uint64_t *n_unitigs, uint64_t *n_bases) {
-  if (!g) return KMI_ERR_INVALID;
-  kmi_ctx *ctx = g->ctx;
-  if (n_unitigs) *n_unitigs = 0;
-  if (n_bases) *n_bases = 0;
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  KMI_TRY(dbg_compact(g, min_edge_count));
-  if (n_unitigs) *n_unitigs = g->n_unitigs;
-  if (n_bases) *n_bases = g->n_unitig_bases;
-  return KMI_OK;
-}
-
-// ... of the union of the ranks' node maps (kmi_unitig_dist.h): collective
-kmi_status kmi_dbg_compact_dist_host(kmi_dbg *g, kmi_comm *comm, uint32_t min_edge_count, uint64_t *n_unitigs_local, uint64_t *n_bases_local,
-                                     uint64_t *n_unitigs_total, uint64_t *n_bases_total) {
-  if (!g) return KMI_ERR_INVALID;
-  if (n_unitigs_local) *n_unitigs_local = 0;
-  if (n_bases_local) *n_bases_local = 0;
-  if (n_unitigs_total) *n_unitigs_total = 0;
-  if (n_bases_total) *n_bases_total = 0;
-  KMI_TRY(dist_check(g->nodes, comm));
-  kmi_ctx *ctx = g->ctx;
-  uint64_t totals[2] = {0, 0};
-  if (alone(ctx, comm)) {
-    KMI_TRY(dbg_compact(g, min_edge_count));
-    totals[0] = g->n_unitigs; totals[1] = g->n_unitig_bases;
-  } else KMI_TRY(kmi::dbg_compact_dist(g, comm, min_edge_count, totals));
-  if (n_unitigs_local) *n_unitigs_local = g->n_unitigs;
-  if (n_bases_local) *n_bases_local = g->n_unitig_bases;
-  if (n_unitigs_total) *n_unitigs_total = totals[0];
-  if (n_bases_total) *n_bases_total = totals[1];
-  return KMI_OK;
-}
-
-kmi_status kmi_dbg_unitigs_export_host(kmi_dbg *g, uint64_t *offsets, char *bases, uint64_t *occurrences, uint8_t *circular,
-                                       size_t capacity_unitigs, size_t capacity_bases) {
-  if (!g) return KMI_ERR_INVALID;
-  kmi_ctx *ctx = g->ctx;
-  if (!g->uni_valid) return set_err(ctx, KMI_ERR_INVALID, "no unitigs: kmi_dbg_compact has not run since the map last changed");
-  const uint64_t nu = g->n_unitigs, nb = g->n_unitig_bases;
-  if ((offsets || occurrences || circular) && capacity_unitigs < nu) return set_err(ctx, KMI_ERR_OVERFLOW, "unitigs export: capacity_unitigs too small");
-  if (bases && capacity_bases < nb) return set_err(ctx, KMI_ERR_OVERFLOW, "unitigs export: capacity_bases too small");
-  if (nu == 0) {
-    if (offsets) offsets[0] = 0;
-    return KMI_OK;
-  }
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  const uint64_t *u_off = (const uint64_t *)g->uni_buf, *u_occ = u_off + nu + 1u;
-  const uint8_t *u_circ = (const uint8_t *)(u_occ + nu);
-  const char *u_bases = (const char *)(u_circ + (((size_t)nu + 15u) & ~(size_t)15u));
-  if (offsets) KMI_HIP(ctx, hipMemcpyAsync(offsets, u_off, (size_t)(nu + 1u) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (occurrences) KMI_HIP(ctx, hipMemcpyAsync(occurrences, u_occ, (size_t)nu * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (circular) KMI_HIP(ctx, hipMemcpyAsync(circular, u_circ, (size_t)nu, hipMemcpyDeviceToHost, ctx->stream));
-  if (bases && nb) KMI_HIP(ctx, hipMemcpyAsync(bases, u_bases, (size_t)nb, hipMemcpyDeviceToHost, ctx->stream));
-  KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return KMI_OK;
-}
-
-// ---- builds over ranks through exchanged super-k-mer records
-kmi_status kmi_index_sk_produce_dev(kmi_index *idx, const uint8_t *bytes_dev, size_t n_bytes, uint32_t nranks, uint64_t *out_records_dev,
-                                    size_t out_capacity, const uint64_t **records_dev, uint64_t *n_records, uint64_t *send_counts_host, int *produced) {
-  if (!idx || !records_dev || !n_records || !send_counts_host || !produced) return KMI_ERR_INVALID;
-  kmi_ctx *ctx = idx->ctx;
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  *produced = 0; *records_dev = nullptr; *n_records = 0;
-  const uint32_t w = sk_width_of(idx);
-  if (!w || !sk_rank_count(nranks)) return KMI_OK;   // not a case of this path: the caller routes k-mers
-  if (ctx->sk_dbg == 7) return KMI_OK;   // (test knob: as if the input had exceeded a capacity of the front end)
-  if (n_bytes) KMI_TRY(align_input(ctx, &bytes_dev, n_bytes));
-  if (!out_records_dev) out_capacity = 0;
-  return sk_produce(idx, w, bytes_dev, n_bytes, nranks, records_dev, n_records, send_counts_host, produced, out_records_dev, out_capacity);
-}
-
-kmi_status kmi_index_sk_consume_dev(kmi_index *idx, const uint64_t *records_dev, size_t n_records, uint32_t nranks) {
-  if (!idx) return KMI_ERR_INVALID;
-  kmi_ctx *ctx = idx->ctx;
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  const uint32_t w = sk_width_of(idx);
-  if (!w || !sk_rank_count(nranks)) return set_err(ctx, KMI_ERR_INVALID, "no super-k-mer build for this index / rank count");
-  if (n_records && !records_dev) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  return sk_consume(idx, w, records_dev, n_records, nranks);
-}
-
-kmi_status kmi_index_set_owner_ranks(kmi_index *idx, uint32_t nranks) {
-  if (!idx) return KMI_ERR_INVALID;
-  if (nranks == 0 || nranks > 8 || (nranks & (nranks - 1u))) return set_err(idx->ctx, KMI_ERR_INVALID, "owner ranks: 1, 2, 4 or 8");
-  if (idx->has_data && idx->n_entries && (1u << idx->owner_lp) != nranks)
-    return set_err(idx->ctx, KMI_ERR_INVALID, "the index holds entries distributed another way");
-  idx->owner_lp = 31u - (uint32_t)__builtin_clz(nranks);
-  return KMI_OK;
-}
-
-kmi_status kmi_index_set_saturating(kmi_index *idx, int on) {
-  if (!idx) return KMI_ERR_INVALID;
-  if (idx->val_words) return set_err(idx->ctx, KMI_ERR_INVALID, "saturating counts belong to the counting maps");
-  idx->saturating = on != 0;
-  return KMI_OK;
-}
-
-kmi_status kmi_index_sk_width(kmi_index *idx, uint32_t *w) {
-  if (!idx || !w) return KMI_ERR_INVALID;
-  *w = kmi::sk_width_of(idx);
-  return KMI_OK;
-}
-
-kmi_status kmi_index_owner_ranks(kmi_index *idx, uint32_t *nranks) {
-  if (!idx || !nranks) return KMI_ERR_INVALID;
-  *nranks = 1u << idx->owner_lp;
-  return KMI_OK;
-}
-
-kmi_status kmi_route_owner_dev(kmi_ctx *ctx, const kmi_config *cfg, const uint64_t *keys_dev, size_t n, uint32_t nranks, uint64_t *out_keys_dev,
-                               uint64_t *send_counts_host) {
-  if (!ctx) return KMI_ERR_INVALID;
-  KShape shape;
-  if (!valid_config(cfg, &shape)) return set_err(ctx, KMI_ERR_INVALID, "bad kmi_config");
-  // (the shape alone, not KMI_FUSED_PATH: an index that is distributed by minimizer owner takes k-mers whatever path built it)
-  if (sk_width_of_shape(shape) == 0 || nranks < 2 || nranks > 8 || (nranks & (nranks - 1u)) || !send_counts_host)
-    return set_err(ctx, KMI_ERR_INVALID, "owner routing is for one-word DNA k-mers over 2, 4 or 8 ranks");
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  for (uint32_t r = 0; r < nranks; ++r) send_counts_host[r] = 0;
-  if (n == 0) return KMI_OK;
-  return route_owner(ctx, cfg, shape, keys_dev, n, nranks, out_keys_dev, send_counts_host);
-}
-
-// ---- update() with a device-side updater (kmi_update.h)
-static kmi_status update_pairs_entry(kmi_index *idx, const uint64_t *records, size_t n, bool on_device, uint32_t op, uint64_t *n_updated) {
-  if (!idx || !n_updated) return KMI_ERR_INVALID;
-  kmi_ctx *ctx = idx->ctx;
-  *n_updated = 0;
-  if (idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "update() is a member of the counting maps");
-  if (op > KMI_UPDATE_ASSIGN) return set_err(ctx, KMI_ERR_INVALID, "unknown updater");
-  if (!on_device) {
-    if (n == 0) return KMI_OK;
-    if (!records) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  }
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  if (n == 0) return KMI_OK;
-  void *dr;   // (the caller's buffer stays as it is)
-  const size_t bytes = n * (idx->shape.n_words + 1) * sizeof(uint64_t);
-  KMI_TRY(ws_get(ctx, WS_INPUT2, bytes + 64, &dr));
-  KMI_HIP(ctx, hipMemcpyAsync(dr, records, bytes, on_device ? hipMemcpyDeviceToDevice : hipMemcpyHostToDevice, ctx->stream));
-  return index_update_pairs(idx, (uint64_t *)dr, n, (int)op, n_updated);
-}
-kmi_status kmi_index_update_pairs_dev(kmi_index *idx, const uint64_t *records_dev, size_t n, uint32_t op, uint64_t *n_updated) {
-  return update_pairs_entry(idx, records_dev, n, true, op, n_updated);
-}
-kmi_status kmi_index_update_pairs_host(kmi_index *idx, const uint64_t *records, size_t n, uint32_t op, uint64_t *n_updated) {
-  return update_pairs_entry(idx, records, n, false, op, n_updated);
-}
-
-// ---- queries in the caller's order (kmi_lookup.h)
-static kmi_status lookup_entry(kmi_index *idx, const uint64_t *queries, size_t nq, uint32_t *counts, bool on_device) {
-  if (!idx) return KMI_ERR_INVALID;
-  kmi_ctx *ctx = idx->ctx;
-  if (idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "lookup() is a member of the count index");
-  if (nq == 0) return KMI_OK;
-  if (!queries || !counts) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  if (on_device) return index_lookup(idx, queries, nq, counts);
-  void *dq, *dc;
-  KMI_TRY(ws_get(ctx, WS_INPUT, nq * idx->shape.n_words * sizeof(uint64_t), &dq));
-  KMI_TRY(ws_get(ctx, WS_OUTPUT, nq * sizeof(uint32_t), &dc));
-  KMI_HIP(ctx, hipMemcpyAsync(dq, queries, nq * idx->shape.n_words * sizeof(uint64_t), hipMemcpyHostToDevice, ctx->stream));
-  KMI_TRY(index_lookup(idx, (const uint64_t *)dq, nq, (uint32_t *)dc));
-  KMI_HIP(ctx, hipMemcpyAsync(counts, dc, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return KMI_OK;
-}
-kmi_status kmi_index_lookup_dev(kmi_index *idx, const uint64_t *queries_dev, size_t nq, uint32_t *counts_dev) {
-  return lookup_entry(idx, queries_dev, nq, counts_dev, true);
-}
-kmi_status kmi_index_lookup_host(kmi_index *idx, const uint64_t *queries, size_t nq, uint32_t *counts) {
-  return lookup_entry(idx, queries, nq, counts, false);
-}
-
-static kmi_status profile_reads_entry(kmi_index *idx, const uint8_t *bytes, size_t n_bytes, bool on_device, uint32_t solid_threshold,
-                                      kmi_read_profile *out, size_t capacity, uint64_t *n_reads) {
-  if (!idx || !n_reads) return KMI_ERR_INVALID;
-  kmi_ctx *ctx = idx->ctx;
-  *n_reads = 0;
-  if (idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "profile_reads() is a member of the count index");
-  if (idx->cfg.seq_format != KMI_FMT_FASTQ) return set_err(ctx, KMI_ERR_INVALID, "profile_reads() reads FASTQ");
-  if (solid_threshold == 0) return set_err(ctx, KMI_ERR_INVALID, "solid_threshold is at least 1");
-  if (n_bytes == 0) return KMI_OK;
-  if (!bytes || (!out && capacity)) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  return index_profile_reads(idx, bytes, n_bytes, on_device, solid_threshold, out, capacity, n_reads);
-}
-kmi_status kmi_index_profile_reads_dev(kmi_index *idx, const uint8_t *bytes_dev, size_t n_bytes, uint32_t solid_threshold, kmi_read_profile *out_dev,
-                                       size_t capacity, uint64_t *n_reads) {
-  return profile_reads_entry(idx, bytes_dev, n_bytes, true, solid_threshold, out_dev, capacity, n_reads);
-}
-kmi_status kmi_index_profile_reads_host(kmi_index *idx, const uint8_t *bytes, size_t n_bytes, uint32_t solid_threshold, kmi_read_profile *out,
-                                        size_t capacity, uint64_t *n_reads) {
-  return profile_reads_entry(idx, bytes, n_bytes, false, solid_threshold, out, capacity, n_reads);
-}
-
-// ---- the position indexes in the caller's order (kmi_locate.h)
-// what a locate over device buffers left, to the caller's host buffers; st = its status (occ and offsets are complete when only the
-// capacity was short)
-static kmi_status locate_download(kmi_index *idx, kmi_status st, size_t nq, uint32_t *occ, const void *dc, uint64_t *offsets, const void *dof,
-                                  uint64_t *values, const void *dv, size_t capacity, const uint64_t *n_hits) {
-  kmi_ctx *ctx = idx->ctx;
-  if (st != KMI_OK && !(st == KMI_ERR_OVERFLOW && *n_hits > capacity)) return st;
-  if (nq) KMI_HIP(ctx, hipMemcpyAsync(occ, dc, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  KMI_HIP(ctx, hipMemcpyAsync(offsets, dof, (nq + 1) * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (st == KMI_OK && values && *n_hits)
-    KMI_HIP(ctx, hipMemcpyAsync(values, dv, *n_hits * idx->val_words * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-  KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return st;
-}
-static kmi_status locate_entry(kmi_index *idx, const uint64_t *queries, size_t nq, bool on_device, uint32_t max_occ, uint32_t *occ, uint64_t *offsets,
-                               uint64_t *values, size_t capacity, uint64_t *n_hits) {
-  if (!idx || !n_hits) return KMI_ERR_INVALID;
-  kmi_ctx *ctx = idx->ctx;
-  *n_hits = 0;
-  if (!idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "locate() is a member of the position indexes");
-  if (max_occ == 0) return set_err(ctx, KMI_ERR_INVALID, "max_occ is at least 1");
-  if (!offsets || (nq && (!queries || !occ)) || (!values && capacity)) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  if (on_device) return index_locate(idx, queries, nq, max_occ, occ, offsets, values, capacity, n_hits);
-  void *dq, *dc, *dof, *dv = nullptr;
-  const size_t q_bytes = nq * idx->shape.n_words * sizeof(uint64_t), v_bytes = capacity * idx->val_words * sizeof(uint64_t);
-  KMI_TRY(ws_get(ctx, WS_INPUT, q_bytes, &dq));
-  KMI_TRY(ws_get(ctx, WS_LOOKUP_CNT, nq * sizeof(uint32_t), &dc));
-  KMI_TRY(ws_get(ctx, WS_LOCATE_OFF, (nq + 1) * sizeof(uint64_t), &dof));
-  if (values) KMI_TRY(ws_get(ctx, WS_OUTPUT2, v_bytes, &dv));
-  if (nq) KMI_HIP(ctx, hipMemcpyAsync(dq, queries, q_bytes, hipMemcpyHostToDevice, ctx->stream));
-  const kmi_status st = index_locate(idx, (const uint64_t *)dq, nq, max_occ, (uint32_t *)dc, (uint64_t *)dof, (uint64_t *)dv, capacity, n_hits);
-  return locate_download(idx, st, nq, occ, dc, offsets, dof, values, dv, capacity, n_hits);
-}
-kmi_status kmi_index_locate_dev(kmi_index *idx, const uint64_t *queries_dev, size_t nq, uint32_t max_occ, uint32_t *occ_dev, uint64_t *offsets_dev,
-                                uint64_t *values_dev, size_t capacity, uint64_t *n_hits) {
-  return locate_entry(idx, queries_dev, nq, true, max_occ, occ_dev, offsets_dev, values_dev, capacity, n_hits);
-}
-kmi_status kmi_index_locate_host(kmi_index *idx, const uint64_t *queries, size_t nq, uint32_t max_occ, uint32_t *occ, uint64_t *offsets,
-                                 uint64_t *values, size_t capacity, uint64_t *n_hits) {
-  return locate_entry(idx, queries, nq, false, max_occ, occ, offsets, values, capacity, n_hits);
-}
-
-static kmi_status seed_reads_entry(kmi_index *idx, const uint8_t *bytes, size_t n_bytes, bool on_device, uint32_t max_occ, kmi_read_seeds *rows,
-                                   size_t cap_reads, uint32_t *occ, uint64_t *offsets, size_t cap_kmers, uint64_t *values, size_t cap_hits,
-                                   uint64_t *n_reads, uint64_t *n_kmers, uint64_t *n_hits) {
-  if (!idx || !n_reads || !n_kmers || !n_hits) return KMI_ERR_INVALID;
-  kmi_ctx *ctx = idx->ctx;
-  *n_reads = *n_kmers = *n_hits = 0;
-  if (!idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "seed_reads() is a member of the position indexes");
-  if (max_occ == 0) return set_err(ctx, KMI_ERR_INVALID, "max_occ is at least 1");
-  if ((n_bytes && !bytes) || (!rows && cap_reads) || ((!occ || !offsets) && cap_kmers) || (!values && cap_hits))
-    return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  return index_seed_reads(idx, bytes, n_bytes, on_device, max_occ, rows, cap_reads, occ, offsets, cap_kmers, values, cap_hits, n_reads, n_kmers, n_hits);
-}
-kmi_status kmi_index_seed_reads_dev(kmi_index *idx, const uint8_t *bytes_dev, size_t n_bytes, uint32_t max_occ, kmi_read_seeds *rows_dev, size_t cap_reads,
-                                    uint32_t *occ_dev, uint64_t *offsets_dev, size_t cap_kmers, uint64_t *values_dev, size_t cap_hits,
-                                    uint64_t *n_reads, uint64_t *n_kmers, uint64_t *n_hits) {
-  return seed_reads_entry(idx, bytes_dev, n_bytes, true, max_occ, rows_dev, cap_reads, occ_dev, offsets_dev, cap_kmers, values_dev, cap_hits, n_reads,
-                          n_kmers, n_hits);
-}
-kmi_status kmi_index_seed_reads_host(kmi_index *idx, const uint8_t *bytes, size_t n_bytes, uint32_t max_occ, kmi_read_seeds *rows, size_t cap_reads,
-                                     uint32_t *occ, uint64_t *offsets, size_t cap_kmers, uint64_t *values, size_t cap_hits, uint64_t *n_reads,
-                                     uint64_t *n_kmers, uint64_t *n_hits) {
-  return seed_reads_entry(idx, bytes, n_bytes, false, max_occ, rows, cap_reads, occ, offsets, cap_kmers, values, cap_hits, n_reads, n_kmers, n_hits);
-}
-
-// ---- the same four over ranks (kmi_query_dist.h). Everything checked here is refused on this rank before anything collective.
-static kmi_status query_dist_check(kmi_index *idx, kmi_comm *comm, bool position, const char *what) {
-  KMI_TRY(dist_check(idx, comm));
-  kmi_ctx *ctx = idx->ctx;
-  if (position != (idx->val_words != 0))
-    return set_err(ctx, KMI_ERR_INVALID, position ? "%s() is a member of the position indexes" : "%s() is a member of the count index", what);
-  if (idx->owner_lp && (1u << idx->owner_lp) != (uint32_t)kmi::comm_size(comm))
-    return set_err(ctx, KMI_ERR_INVALID, "%s(): the index is distributed over another number of owner ranks than the communicator has", what);
-  return KMI_OK;
-}
-
-static kmi_status lookup_dist_entry(kmi_index *idx, kmi_comm *comm, const uint64_t *queries, size_t nq, uint32_t *counts, bool on_device) {
-  KMI_TRY(query_dist_check(idx, comm, false, "lookup"));
-  kmi_ctx *ctx = idx->ctx;
-  if (nq && (!queries || !counts)) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  if (alone(ctx, comm)) return lookup_entry(idx, queries, nq, counts, on_device);
-  if (on_device) return index_lookup_dist(idx, comm, queries, nq, counts);
-  void *dq = nullptr, *dc = nullptr;
-  const size_t q_bytes = nq * idx->shape.n_words * sizeof(uint64_t);
-  const kmi_status staged = [&]() -> kmi_status {
-    KMI_TRY(ws_get(ctx, WS_INPUT, q_bytes + 64, &dq));
-    KMI_TRY(ws_get(ctx, WS_OUTPUT, nq * sizeof(uint32_t) + 64, &dc));
-    if (nq) KMI_HIP(ctx, hipMemcpyAsync(dq, queries, q_bytes, hipMemcpyHostToDevice, ctx->stream));
-    return KMI_OK;
-  }();
-  if (staged != KMI_OK) { uint64_t more = 0, want = 0; return qd_agree(comm, staged, &more, &want); }   // (the peers are told in their first all-reduce)
-  KMI_TRY(index_lookup_dist(idx, comm, (const uint64_t *)dq, nq, (uint32_t *)dc));
-  if (nq) KMI_HIP(ctx, hipMemcpyAsync(counts, dc, nq * sizeof(uint32_t), hipMemcpyDeviceToHost, ctx->stream));
-  KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return KMI_OK;
-}
-kmi_status kmi_index_lookup_dist_dev(kmi_index *idx, kmi_comm *comm, const uint64_t *queries_dev, size_t nq, uint32_t *counts_dev) {
-  return lookup_dist_entry(idx, comm, queries_dev, nq, counts_dev, true);
-}
-kmi_status kmi_index_lookup_dist_host(kmi_index *idx, kmi_comm *comm, const uint64_t *queries, size_t nq, uint32_t *counts) {
-  return lookup_dist_entry(idx, comm, queries, nq, counts, false);
-}
-
-static kmi_status profile_reads_dist_entry(kmi_index *idx, kmi_comm *comm, const uint8_t *bytes, size_t n_bytes, bool on_device, uint32_t solid_threshold,
-                                           kmi_read_profile *out, size_t capacity, uint64_t *n_reads) {
-  if (!n_reads) return KMI_ERR_INVALID;
-  *n_reads = 0;
-  KMI_TRY(query_dist_check(idx, comm, false, "profile_reads"));
-  kmi_ctx *ctx = idx->ctx;
-  if (idx->cfg.seq_format != KMI_FMT_FASTQ) return set_err(ctx, KMI_ERR_INVALID, "profile_reads() reads FASTQ");
-  if (solid_threshold == 0) return set_err(ctx, KMI_ERR_INVALID, "solid_threshold is at least 1");
-  if ((n_bytes && !bytes) || (!out && capacity)) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  if (alone(idx->ctx, comm))
-    return on_device ? kmi_index_profile_reads_dev(idx, bytes, n_bytes, solid_threshold, out, capacity, n_reads)
-                     : kmi_index_profile_reads_host(idx, bytes, n_bytes, solid_threshold, out, capacity, n_reads);
-  return index_profile_reads_dist(idx, comm, bytes, n_bytes, on_device, solid_threshold, out, capacity, n_reads);
-}
-kmi_status kmi_index_profile_reads_dist_dev(kmi_index *idx, kmi_comm *comm, const uint8_t *bytes_dev, size_t n_bytes, uint32_t solid_threshold,
-                                            kmi_read_profile *out_dev, size_t capacity, uint64_t *n_reads) {
-  return profile_reads_dist_entry(idx, comm, bytes_dev, n_bytes, true, solid_threshold, out_dev, capacity, n_reads);
-}
-kmi_status kmi_index_profile_reads_dist_host(kmi_index *idx, kmi_comm *comm, const uint8_t *bytes, size_t n_bytes, uint32_t solid_threshold,
-                                             kmi_read_profile *out, size_t capacity, uint64_t *n_reads) {
-  return profile_reads_dist_entry(idx, comm, bytes, n_bytes, false, solid_threshold, out, capacity, n_reads);
-}
-
-static kmi_status locate_dist_entry(kmi_index *idx, kmi_comm *comm, const uint64_t *queries, size_t nq, bool on_device, uint32_t max_occ, uint32_t *occ,
-                                    uint64_t *offsets, uint64_t *values, size_t capacity, uint64_t *n_hits) {
-  if (!n_hits) return KMI_ERR_INVALID;
-  *n_hits = 0;
-  KMI_TRY(query_dist_check(idx, comm, true, "locate"));
-  kmi_ctx *ctx = idx->ctx;
-  if (max_occ == 0) return set_err(ctx, KMI_ERR_INVALID, "max_occ is at least 1");
-  if (!offsets || (nq && (!queries || !occ)) || (!values && capacity)) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  if (alone(ctx, comm)) return locate_entry(idx, queries, nq, on_device, max_occ, occ, offsets, values, capacity, n_hits);
-  if (on_device) return index_locate_dist(idx, comm, queries, nq, max_occ, occ, offsets, values, capacity, n_hits);
-  void *dq = nullptr, *dc = nullptr, *dof = nullptr, *dv = nullptr;
-  const size_t q_bytes = nq * idx->shape.n_words * sizeof(uint64_t), v_bytes = capacity * idx->val_words * sizeof(uint64_t);
-  const kmi_status staged = [&]() -> kmi_status {
-    KMI_TRY(ws_get(ctx, WS_INPUT, q_bytes + 64, &dq));
-    KMI_TRY(ws_get(ctx, WS_OUTPUT, nq * sizeof(uint32_t) + 64, &dc));
-    KMI_TRY(ws_get(ctx, WS_LOCATE_OFF, (nq + 1) * sizeof(uint64_t), &dof));
-    if (values) KMI_TRY(ws_get(ctx, WS_OUTPUT2, v_bytes + 64, &dv));
-    if (nq) KMI_HIP(ctx, hipMemcpyAsync(dq, queries, q_bytes, hipMemcpyHostToDevice, ctx->stream));
-    return KMI_OK;
-  }();
-  if (staged != KMI_OK) { uint64_t more = 0, want = 0; return qd_agree(comm, staged, &more, &want); }   // (the peers are told in their first all-reduce)
-  const kmi_status st = index_locate_dist(idx, comm, (const uint64_t *)dq, nq, max_occ, (uint32_t *)dc, (uint64_t *)dof, (uint64_t *)dv, capacity, n_hits);
-  return locate_download(idx, st, nq, occ, dc, offsets, dof, values, dv, capacity, n_hits);
-}
-kmi_status kmi_index_locate_dist_dev(kmi_index *idx, kmi_comm *comm, const uint64_t *queries_dev, size_t nq, uint32_t max_occ, uint32_t *occ_dev,
-                                     uint64_t *offsets_dev, uint64_t *values_dev, size_t capacity, uint64_t *n_hits) {
-  return locate_dist_entry(idx, comm, queries_dev, nq, true, max_occ, occ_dev, offsets_dev, values_dev, capacity, n_hits);
-}
-kmi_status kmi_index_locate_dist_host(kmi_index *idx, kmi_comm *comm, const uint64_t *queries, size_t nq, uint32_t max_occ, uint32_t *occ,
-                                      uint64_t *offsets, uint64_t *values, size_t capacity, uint64_t *n_hits) {
-  return locate_dist_entry(idx, comm, queries, nq, false, max_occ, occ, offsets, values, capacity, n_hits);
-}
-
-static kmi_status seed_reads_dist_entry(kmi_index *idx, kmi_comm *comm, const uint8_t *bytes, size_t n_bytes, bool on_device, uint32_t max_occ,
-                                        kmi_read_seeds *rows, size_t cap_reads, uint32_t *occ, uint64_t *offsets, size_t cap_kmers, uint64_t *values,
-                                        size_t cap_hits, uint64_t *n_reads, uint64_t *n_kmers, uint64_t *n_hits) {
-  if (!n_reads || !n_kmers || !n_hits) return KMI_ERR_INVALID;
-  *n_reads = *n_kmers = *n_hits = 0;
-  KMI_TRY(query_dist_check(idx, comm, true, "seed_reads"));
-  kmi_ctx *ctx = idx->ctx;
-  if (max_occ == 0) return set_err(ctx, KMI_ERR_INVALID, "max_occ is at least 1");
-  if ((n_bytes && !bytes) || (!rows && cap_reads) || ((!occ || !offsets) && cap_kmers) || (!values && cap_hits))
-    return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  if (alone(idx->ctx, comm))
-    return seed_reads_entry(idx, bytes, n_bytes, on_device, max_occ, rows, cap_reads, occ, offsets, cap_kmers, values, cap_hits, n_reads, n_kmers, n_hits);
-  return index_seed_reads_dist(idx, comm, bytes, n_bytes, on_device, max_occ, rows, cap_reads, occ, offsets, cap_kmers, values, cap_hits, n_reads,
-                               n_kmers, n_hits);
-}
-kmi_status kmi_index_seed_reads_dist_dev(kmi_index *idx, kmi_comm *comm, const uint8_t *bytes_dev, size_t n_bytes, uint32_t max_occ,
-                                         kmi_read_seeds *rows_dev, size_t cap_reads, uint32_t *occ_dev, uint64_t *offsets_dev, size_t cap_kmers,
-                                         uint64_t *values_dev, size_t cap_hits, uint64_t *n_reads, uint64_t *n_kmers, uint64_t *n_hits) {
-  return seed_reads_dist_entry(idx, comm, bytes_dev, n_bytes, true, max_occ, rows_dev, cap_reads, occ_dev, offsets_dev, cap_kmers, values_dev, cap_hits,
-                               n_reads, n_kmers, n_hits);
-}
-kmi_status kmi_index_seed_reads_dist_host(kmi_index *idx, kmi_comm *comm, const uint8_t *bytes, size_t n_bytes, uint32_t max_occ, kmi_read_seeds *rows,
-                                          size_t cap_reads, uint32_t *occ, uint64_t *offsets, size_t cap_kmers, uint64_t *values, size_t cap_hits,
-                                          uint64_t *n_reads, uint64_t *n_kmers, uint64_t *n_hits) {
-  return seed_reads_dist_entry(idx, comm, bytes, n_bytes, false, max_occ, rows, cap_reads, occ, offsets, cap_kmers, values, cap_hits, n_reads, n_kmers,
-                               n_hits);
-}
-
-// ---- count spectrum and count filter (kmi_spectrum.h)
-static kmi_status spectrum_entry(kmi_index *idx, uint32_t n_bins, uint64_t *hist, bool on_device, kmi_spectrum_totals *totals) {
-  if (!idx) return KMI_ERR_INVALID;
-  kmi_ctx *ctx = idx->ctx;
-  if (idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "spectrum() is a member of the count index");
-  if (n_bins < 2 || n_bins > (uint32_t)KMI_SPECTRUM_MAX_BINS) return set_err(ctx, KMI_ERR_INVALID, "n_bins is 2 .. KMI_SPECTRUM_MAX_BINS");
-  if (!hist) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  uint64_t *d_hist = hist;
-  if (!on_device) {
-    void *p;
-    KMI_TRY(ws_get(ctx, WS_OUTPUT, n_bins * sizeof(uint64_t), &p));
-    d_hist = (uint64_t *)p;
-  }
-  KMI_TRY(spectrum_run(idx, n_bins, d_hist));
-  if (!on_device) KMI_HIP(ctx, hipMemcpyAsync(hist, d_hist, n_bins * sizeof(uint64_t), hipMemcpyDeviceToHost, ctx->stream));
-  if (totals) KMI_TRY(spectrum_totals(idx, totals));
-  else if (!on_device) KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
-  return KMI_OK;
-}
-kmi_status kmi_index_spectrum_dev(kmi_index *idx, uint32_t n_bins, uint64_t *hist_dev, kmi_spectrum_totals *totals) {
-  return spectrum_entry(idx, n_bins, hist_dev, true, totals);
-}
-kmi_status kmi_index_spectrum_host(kmi_index *idx, uint32_t n_bins, uint64_t *hist, kmi_spectrum_totals *totals) {
-  return spectrum_entry(idx, n_bins, hist, false, totals);
-}
-
-kmi_status kmi_index_spectrum_dist_host(kmi_index *idx, kmi_comm *comm, uint32_t n_bins, uint64_t *hist, kmi_spectrum_totals *totals) {
-  KMI_TRY(dist_check(idx, comm));
-  kmi_ctx *ctx = idx->ctx;
-  // (argument errors are every rank's alike: nothing collective has started)
-  if (idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "spectrum() is a member of the count index");
-  if (n_bins < 2 || n_bins > (uint32_t)KMI_SPECTRUM_MAX_BINS) return set_err(ctx, KMI_ERR_INVALID, "n_bins is 2 .. KMI_SPECTRUM_MAX_BINS");
-  if (!hist) return set_err(ctx, KMI_ERR_INVALID, "null buffer");
-  // the bins, then n_entries and sum_counts: one sum over the ranks; the largest count and ~(the smallest): one maximum
-  std::vector<uint64_t> words((size_t)n_bins + 2, 0);
-  kmi_spectrum_totals t{};
-  const kmi_status mine = spectrum_entry(idx, n_bins, words.data(), false, &t);
-  KMI_TRY(dist_agree(comm, mine));   // a rank whose pass failed does not leave the others in the all-reduce
-  words[n_bins] = t.n_entries; words[(size_t)n_bins + 1] = t.sum_counts;
-  uint64_t ext[2] = {t.max_count, t.n_entries ? (uint64_t)(uint32_t)~t.min_count : 0ull};   // (a rank without entries has no say in either)
-  KMI_TRY(kmi::comm_allreduce_sum(comm, words.data(), words.size()));
-  KMI_TRY(kmi::comm_allreduce(comm, ext, 2, 1));
-  memcpy(hist, words.data(), sizeof(uint64_t) * n_bins);
-  if (totals) {
-    totals->n_entries = words[n_bins]; totals->sum_counts = words[(size_t)n_bins + 1];
-    totals->max_count = (uint32_t)ext[0];
-    totals->min_count = totals->n_entries ? ~(uint32_t)ext[1] : 0u;
-  }
-  return KMI_OK;
-}
-
-kmi_status kmi_index_retain_counts(kmi_index *idx, uint32_t lo, uint32_t hi, uint64_t *n_erased) {
-  if (!idx) return KMI_ERR_INVALID;
-  kmi_ctx *ctx = idx->ctx;
-  if (n_erased) *n_erased = 0;
-  if (idx->val_words) return set_err(ctx, KMI_ERR_INVALID, "retain_counts() is a member of the count index");
-  if (lo > hi) return set_err(ctx, KMI_ERR_INVALID, "retain_counts: lo > hi");
-  ctx->retain_fullest = 0;
-  if (!idx->has_data || idx->n_entries == 0) return KMI_OK;
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  return index_retain_counts(idx, lo, hi, n_erased);
-}
-
-// ---- cleaning a de Bruijn node map (kmi_dbg_clean.h)
-// the node index is a count index whose values are the occurrences: its own spectrum entry points do the work
-static kmi_status dbg_has_occurrences(kmi_dbg *g) {
-  if (g->node_kind == KMI_DBG_EDGE_EXISTS) return set_err(g->ctx, KMI_ERR_INVALID, "spectrum: an EDGE_EXISTS map keeps no occurrence count");
-  return KMI_OK;
-}
-kmi_status kmi_dbg_spectrum_host(kmi_dbg *g, uint32_t n_bins, uint64_t *hist, kmi_spectrum_totals *totals) {
-  if (!g) return KMI_ERR_INVALID;
-  KMI_TRY(dbg_has_occurrences(g));
-  return kmi_index_spectrum_host(g->nodes, n_bins, hist, totals);
-}
-
-kmi_status kmi_dbg_spectrum_dist_host(kmi_dbg *g, kmi_comm *comm, uint32_t n_bins, uint64_t *hist, kmi_spectrum_totals *totals) {
-  if (!g) return KMI_ERR_INVALID;
-  KMI_TRY(dist_check(g->nodes, comm));
-  KMI_TRY(dbg_has_occurrences(g));   // (every rank's alike: nothing collective has started)
-  return kmi_index_spectrum_dist_host(g->nodes, comm, n_bins, hist, totals);
-}
-
-kmi_status kmi_dbg_retain_counts(kmi_dbg *g, uint32_t lo, uint32_t hi, uint64_t *n_erased) {
-  if (!g) return KMI_ERR_INVALID;
-  return kmi::dbg_retain_counts(g, lo, hi, n_erased);
-}
-
-kmi_status kmi_dbg_prune_edges(kmi_dbg *g, uint32_t min_edge_count, kmi_dbg_prune_stats *stats) {
-  if (!g) return KMI_ERR_INVALID;
-  uint64_t s[8];
-  const kmi_status st = kmi::dbg_prune(g, min_edge_count, s);
-  if (stats) memcpy(stats, s, sizeof(s));
-  return st;
-}
-
-kmi_status kmi_dbg_prune_edges_dist_host(kmi_dbg *g, kmi_comm *comm, uint32_t min_edge_count, kmi_dbg_prune_stats *stats_local,
-                                         kmi_dbg_prune_stats *stats_total) {
-  if (!g) return KMI_ERR_INVALID;
-  if (stats_local) memset(stats_local, 0, sizeof(*stats_local));
-  if (stats_total) memset(stats_total, 0, sizeof(*stats_total));
-  KMI_TRY(dist_check(g->nodes, comm));
-  uint64_t sl[8], stt[8];
-  kmi_status st;
-  if (alone(g->ctx, comm)) {
-    st = kmi::dbg_prune(g, min_edge_count, sl);
-    memcpy(stt, sl, sizeof(sl));
-  } else st = kmi::dbg_prune_dist(g, comm, min_edge_count, sl, stt);
-  if (stats_local) memcpy(stats_local, sl, sizeof(sl));
-  if (stats_total) memcpy(stats_total, stt, sizeof(stt));
-  return st;
-}
-
-// ---- two count indexes compared and combined (kmi_setops.h)
-kmi_status kmi_index_compare(kmi_index *a, kmi_index *b, kmi_index_overlap *out) {
-  if (!a || !b || !out) return KMI_ERR_INVALID;
-  kmi_ctx *ctx = a->ctx;
-  memset(out, 0, sizeof(*out));
-  KMI_TRY(setops_check(a, b, "compare"));
-  ctx->setops_npass = 0;
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  const kmi_status st = index_compare(a, b, out);
-  if (st != KMI_OK) memset(out, 0, sizeof(*out));
-  return st;
-}
-
-kmi_status kmi_index_compare_dist_host(kmi_index *a, kmi_index *b, kmi_comm *comm, kmi_index_overlap *out) {
-  KMI_TRY(dist_check(a, comm));
-  // (argument errors are every rank's alike: nothing collective has started)
-  if (!b || !out) return KMI_ERR_INVALID;
-  memset(out, 0, sizeof(*out));
-  KMI_TRY(setops_check(a, b, "compare"));
-  kmi_index_overlap mine_words{};
-  const kmi_status mine = kmi_index_compare(a, b, &mine_words);
-  KMI_TRY(dist_agree(comm, mine));   // a rank whose join failed does not leave the others in the all-reduce
-  static_assert(sizeof(kmi_index_overlap) == 8 * sizeof(uint64_t), "eight words");
-  uint64_t words[8];
-  memcpy(words, &mine_words, sizeof(words));
-  KMI_TRY(kmi::comm_allreduce_sum(comm, words, 8));
-  memcpy(out, words, sizeof(words));
-  return KMI_OK;
-}
-
-kmi_status kmi_index_combine(kmi_index *a, kmi_index *b, uint32_t op, uint64_t *n_entries) {
-  if (!a || !b) return KMI_ERR_INVALID;
-  kmi_ctx *ctx = a->ctx;
-  if (n_entries) *n_entries = a->has_data ? a->n_entries : 0;
-  KMI_TRY(setops_check(a, b, "combine"));
-  if (op > (uint32_t)KMI_COMBINE_SUBTRACT_COUNTS) return set_err(ctx, KMI_ERR_INVALID, "combine: unknown op");
-  if (a == b) return set_err(ctx, KMI_ERR_INVALID, "combine: a and b are the same index");
-  KMI_HIP(ctx, hipSetDevice(ctx->device));
-  const kmi_status st = index_combine(a, b, op);
-  if (n_entries) *n_entries = a->has_data ? a->n_entries : 0;
-  return st;
-}
-
-}  // extern "C"
+// The rest of the C ABI, as headers of this translation unit (the entry points share static templates with everything above, so they
+// are not units of their own). Each opens and closes its own extern "C"; all use the host glue (alone, stage_host, results_to_host,
+// fastq_range_cut) and the collectives' helpers (dist_check, dist_exchange, keys_to_owners, dist_agree, dist_state) above.
+#include "kmi_abi_dist_build.h"   // builds over ranks, FASTQ / FASTA byte ranges, count / find / erase / size over ranks; needs kmi_query_dist.h
+#include "kmi_abi_dbg.h"          // the kmi_dbg_* entries; needs fasta_range_partition of kmi_abi_dist_build.h
+#include "kmi_abi_ordered.h"      // sk produce / consume, update pairs, lookup / profile / locate / seed entries; needs kmi_query_dist.h
+#include "kmi_abi_analysis.h"     // spectrum, retain, de Bruijn cleaning, compare / combine entries
