@@ -314,6 +314,15 @@ class NodeIndex {
     return total;
   }
 
+  // clip_tips: one round of tip clipping (kmi_dbg_clip_tips): dead-end unitigs of at most max_tip_nodes nodes that hang off a
+  // junction with a greater branch leave the map with their junction counters; flags: KMI_DBG_CLIP_ISLANDS. One rank only: there is
+  // no form over ranks, and a map that holds a rank's share of a build over ranks is refused (KMI_ERR_INVALID, thrown).
+  kmi_dbg_clip_stats clip_tips(uint32_t min_edge_count = 1, uint32_t max_tip_nodes = 2 * KmerType::size, uint32_t flags = 0) {
+    kmi_dbg_clip_stats s{};
+    ::kmerind::check(ctx, kmi_dbg_clip_tips(g, min_edge_count, max_tip_nodes, flags, &s));
+    return s;
+  }
+
   kmi_ctx *context() const { return ctx; }
 
  private:

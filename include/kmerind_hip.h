@@ -919,6 +919,53 @@ kmi_status kmi_dbg_prune_edges(kmi_dbg *g, uint32_t min_edge_count, kmi_dbg_prun
 kmi_status kmi_dbg_prune_edges_dist_host(kmi_dbg *g, kmi_comm *comm, uint32_t min_edge_count, kmi_dbg_prune_stats *stats_local,
                                          kmi_dbg_prune_stats *stats_total);
 
+/* ---- clipping tips: short dead-end unitigs that hang off a junction (no counterpart in the reference)
+ * The count filter and the pruning above remove what is rare; an error near a read's end that is seen often enough to pass the
+ * filter survives them as a dead-end chain of a few nodes, and the junction it hangs off splits the true path into three unitigs.
+ * kmi_dbg_clip_tips removes such chains. With t = min_edge_count >= 1 and M = max_tip_nodes >= 1; counters are read as the
+ * compaction reads them (0 / 1 for an EDGE_EXISTS map); everything is judged against the map AS IT WAS WHEN THE CALL BEGAN, so one
+ * call is one round and a pure function of the map:
+ *  1. Unitigs. Those of kmi_dbg_compact with threshold t (its rules 1-4). Cycles are never clipped. A path unitig X has two ends:
+ *     the ends of its first and of its last node that its links do not use (both ends of the node when X is a single node). The
+ *     degree of an end is rule 1's of the compaction.
+ *  2. Island. X has at most M nodes and both its ends have degree 0. Counted; removed only with KMI_DBG_CLIP_ISLANDS.
+ *  3. Candidate. X has at most M nodes; one end is dead (degree 0); the other end (v, E) has degree exactly 1, with base b; the
+ *     neighbour w of the counter (v, E, b) -- the pruning's definition above -- is a node and not a node of X; and the reciprocal
+ *     counter (w, E', b') is >= t. That counter is X's junction counter and (w, E') its junction end. X is not linked into w, so on
+ *     a pruned map (w, E') has degree >= 2.
+ *  4. Verdict. The counters >= t at a junction end are ordered by the key (value, 1 if the counter is NOT the junction counter of a
+ *     candidate else 0, -base index). A candidate is clipped if and only if another counter >= t of its junction end has a greater
+ *     key. So the greatest branch of every end always stays and a junction is never eroded to nothing; a real continuation beats
+ *     a tip of equal weight; of two tips of equal weight the one with the smaller base stays.
+ *  5. Effect, as in retain_counts. The nodes of the clipped tips, and of the islands when asked, leave the map; the junction
+ *     counter of every clipped tip is cleared, in a node that stays; every other counter and every counts[8] keeps its value bit
+ *     for bit; the survivors keep their order, in fresh arrays of exactly the surviving size. When nothing leaves, the map stays
+ *     as it is.
+ * Consequences. A candidate's junction node never lies in a clipped unitig: the ends of a candidate and of an island have degrees
+ * 0 and at most 1, and a clipped tip's junction end has degree >= 2 (its junction counter and the greater one). So on a map where
+ * prune_edges(t) clears nothing and no node is its own reverse complement (any odd k), a round leaves no counter that points at a
+ * removed node, and prune_edges(t) clears nothing on the result either. (For even k the exemption of the pruning's rule 3 breaks
+ * this: a counter beside a palindromic node need not be reciprocated.) A tip longer than M nodes stays; the usual M is 2 k. One
+ * round can uncover new tips (a tip on a tip): call again, with prune_edges in between, until n_tips_clipped is 0.
+ * KMI_ERR_INVALID: t = 0; M = 0; flag bits other than KMI_DBG_CLIP_ISLANDS; an alphabet that is not 2-bit; a map that holds one
+ * rank's share of a build over ranks (as kmi_dbg_compact and kmi_dbg_prune_edges refuse it). KMI_ERR_OVERFLOW: 2^31 - 1 nodes or
+ * more. An empty map gives zeros. On any error the map holds what it held, and so does the result of an earlier compaction; a call
+ * that succeeds drops it. The call is complete on return. There is NO form over ranks: it needs the end records of the compaction
+ * over ranks and a request / answer exchange like the pruning's. */
+enum { KMI_DBG_CLIP_ISLANDS = 1u };
+typedef struct {
+  uint64_t n_nodes;            /* nodes of the map when the call began */
+  uint64_t n_unitigs;          /* unitigs of that map under t (paths and cycles): what kmi_dbg_compact(t) would report */
+  uint64_t n_candidates;       /* rule 3 */
+  uint64_t n_tips_clipped;     /* candidates removed by rule 4 */
+  uint64_t n_islands;          /* rule 2 */
+  uint64_t n_islands_removed;  /* = n_islands with KMI_DBG_CLIP_ISLANDS, else 0 */
+  uint64_t n_nodes_removed;
+  uint64_t n_counters_cleared; /* junction counters of clipped tips, cleared in surviving nodes */
+} kmi_dbg_clip_stats;  /* 64 bytes */
+kmi_status kmi_dbg_clip_tips(kmi_dbg *g, uint32_t min_edge_count, uint32_t max_tip_nodes, uint32_t flags,
+                             kmi_dbg_clip_stats *stats /* may be NULL */);
+
 /* ---- measurement support --------------------------------------------------- */
 /* per-kernel HIP-event timing on the context's stream (bench.py roofline leg) */
 kmi_status kmi_profile_enable(kmi_ctx *ctx, int on);

@@ -60,6 +60,14 @@ class DbgPruneStats(C.Structure):
                                           "n_requests")]
 
 
+class DbgClipStats(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("n_nodes", "n_unitigs", "n_candidates", "n_tips_clipped", "n_islands", "n_islands_removed",
+                                          "n_nodes_removed", "n_counters_cleared")]
+
+
+DBG_CLIP_ISLANDS = 1   # KMI_DBG_CLIP_ISLANDS
+
+
 class IndexOverlap(C.Structure):
     _fields_ = [("n_a", C.c_uint64), ("n_b", C.c_uint64), ("n_shared", C.c_uint64), ("sum_a", C.c_uint64), ("sum_b", C.c_uint64),
                 ("sum_a_shared", C.c_uint64), ("sum_b_shared", C.c_uint64), ("sum_min_shared", C.c_uint64)]
@@ -224,6 +232,7 @@ SIGNATURES = {
     "kmi_dbg_retain_counts": (C.c_int, [_P, _u32, _u32, C.POINTER(_u64)]),
     "kmi_dbg_prune_edges": (C.c_int, [_P, _u32, C.POINTER(DbgPruneStats)]),
     "kmi_dbg_prune_edges_dist_host": (C.c_int, [_P, _P, _u32, C.POINTER(DbgPruneStats), C.POINTER(DbgPruneStats)]),
+    "kmi_dbg_clip_tips": (C.c_int, [_P, _u32, _u32, _u32, C.POINTER(DbgClipStats)]),
     "kmi_dbg_compact": (C.c_int, [_P, _u32, C.POINTER(_u64), C.POINTER(_u64)]),
     "kmi_dbg_compact_dist_host": (C.c_int, [_P, _P, _u32, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
     "kmi_dbg_unitigs_export_host": (C.c_int, [_P, _P, _P, _P, _P, _sz, _sz]),

@@ -708,7 +708,7 @@ class DeBruijnNodes:
                                                        nu.value, nb.value))
         return offsets, bases[:nb.value], occ[:nu.value], circ[:nu.value].astype(bool)
 
-    # ---- cleaning the map on the device (kmi_dbg_spectrum_* / kmi_dbg_retain_counts / kmi_dbg_prune_edges*)
+    # ---- cleaning the map on the device (kmi_dbg_spectrum_* / kmi_dbg_retain_counts / kmi_dbg_prune_edges* / kmi_dbg_clip_tips)
     def spectrum(self, n_bins=256, comm=None):
         """(hist, totals) of the nodes' occurrence counts (counts[8]): hist[min(count, n_bins - 1)] counts the nodes
         (np.uint64[n_bins]); totals is a dict of n_entries, sum_counts, min_count, max_count. With `comm` the call is collective and
@@ -743,6 +743,16 @@ class DeBruijnNodes:
             self.ctx.check(lib.kmi_dbg_prune_edges(self.h, int(min_edge_count), C.byref(s)))
             self.prune_totals = {f: getattr(s, f) for f in names}
         return {f: getattr(s, f) for f in names}
+
+    def clip_tips(self, min_edge_count=1, max_tip_nodes=None, islands=False):
+        """One round of tip clipping (kmi_dbg_clip_tips; the definition is in include/kmerind_hip.h): dead-end unitigs of at most
+        max_tip_nodes nodes (None: 2 k) that hang off a junction with a greater branch leave the map, and their junction counters
+        are cleared; islands=True also removes the short unitigs without any neighbour -> dict of the kmi_dbg_clip_stats words. One
+        rank only: a map that holds a rank's share of a build over ranks is refused."""
+        m = 2 * int(self.cfg.k) if max_tip_nodes is None else int(max_tip_nodes)
+        s = L.DbgClipStats()
+        self.ctx.check(lib.kmi_dbg_clip_tips(self.h, int(min_edge_count), m, L.DBG_CLIP_ISLANDS if islands else 0, C.byref(s)))
+        return {f: getattr(s, f) for f, _ in L.DbgClipStats._fields_}
 
     def unitig_sequences(self, min_edge_count=1, comm=None):
         """the sequences of unitigs() as a list of bytes, in unitig order"""

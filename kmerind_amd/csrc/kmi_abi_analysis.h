@@ -1,6 +1,6 @@
 // kmi_abi_analysis.h -- spectrum and retain, the de Bruijn node map's cleaning, compare / combine of two count indexes.
 //
-// Included by kmi_index.hip last (kmi_spectrum.h, kmi_dbg_clean.h and kmi_setops.h hold what it calls; alone,
+// Included by kmi_index.hip last (kmi_spectrum.h, kmi_dbg_clean.h, kmi_dbg_tips.h and kmi_setops.h hold what it calls; alone,
 // dist_check and dist_agree are kmi_index.hip's own).
 #pragma once
 
@@ -116,6 +116,15 @@ kmi_status kmi_dbg_prune_edges_dist_host(kmi_dbg *g, kmi_comm *comm, uint32_t mi
   } else st = kmi::dbg_prune_dist(g, comm, min_edge_count, sl, stt);
   if (stats_local) memcpy(stats_local, sl, sizeof(sl));
   if (stats_total) memcpy(stats_total, stt, sizeof(stt));
+  return st;
+}
+
+kmi_status kmi_dbg_clip_tips(kmi_dbg *g, uint32_t min_edge_count, uint32_t max_tip_nodes, uint32_t flags, kmi_dbg_clip_stats *stats) {
+  if (!g) return KMI_ERR_INVALID;
+  static_assert(sizeof(kmi_dbg_clip_stats) == 8 * sizeof(uint64_t), "eight words");
+  uint64_t s[8];
+  const kmi_status st = kmi::dbg_clip_tips(g, min_edge_count, max_tip_nodes, flags, s);
+  if (stats) memcpy(stats, s, sizeof(s));
   return st;
 }
 

@@ -66,7 +66,8 @@ enum WsSlot {
   WS_UNI_STAGE,       // ... staged 16-byte records of every state before they are grouped by rank; the link requests
   WS_UNI_END,         // ... cycle candidates, then the end k-mer and end occurrences of every state
   WS_UNI_CNT,         // ... records per destination rank, cursors, device scalars
-  WS_LOOKUP_RECS,     // positional lookup / read profile (kmi_lookup.h): (key words, tag) records of the queries or of a batch's k-mers
+  WS_DBG_TIPS,        // tip clipping (kmi_dbg_tips.h): device scalars, survivors of every fine bucket, per-unitig junctions, per-node masks and classes
+  WS_LOOKUP_RECS,    // positional lookup / read profile (kmi_lookup.h): (key words, tag) records of the queries or of a batch's k-mers
   WS_LOOKUP_CNT,      // ... the looked-up count of every k-mer of a batch, in file order
   WS_SPECTRUM,        // count spectrum / count filter (kmi_spectrum.h): the call's device scalars, then the survivors of every fine bucket
   WS_LOCATE_POS,      // locate / seed_reads (kmi_locate.h): entry positions of every fine bucket grouped by key, one u32 per index entry

@@ -368,8 +368,17 @@ static kmi_status uni_rank_rounds(kmi_dbg *g, ulonglong2 *rank2, uint64_t half, 
   return KMI_OK;
 }
 
+// what the stages up to unitig_heads leave in the workspace, for kmi_dbg_compact and for kmi_dbg_clip_tips (kmi_dbg_tips.h)
+struct UniStages {
+  uint32_t *tab; uint64_t mask;   // the neighbour table
+  ulonglong2 *rk;                 // final ranking records: rk[s] = (end state | distance << 32, occurrence sum)
+  ulonglong2 *scan;               // per node (1, bases) for a head, (0, 0) for the others; the scan's tile sums fit behind n
+  uint8_t *dir, *circ;            // per node: spelling direction, circular flag
+};
+
+// table, links, jumping, cycle pass, heads
 template <int NW>
-static kmi_status dbg_compact_impl(kmi_dbg *g, uint32_t t) {
+static kmi_status uni_stages(kmi_dbg *g, uint32_t t, UniStages *out) {
   kmi_ctx *ctx = g->ctx;
   kmi_index *idx = g->nodes;
   const KShape shape = g->shape;
@@ -433,12 +442,30 @@ static kmi_status dbg_compact_impl(kmi_dbg *g, uint32_t t) {
     KMI_TRY(uni_rank_rounds(g, rank2, half, ns, &d_scalars[0], &cur));
     rk = rank2 + cur * half;
   }
-  ulonglong2 *scan = rank2 + (1u - cur) * half, *sums = scan + n;
-  const uint64_t n_tiles = (n + kUniScanTile - 1) / kUniScanTile;
+  ulonglong2 *scan = rank2 + (1u - cur) * half;
   {
     ProfScope ps(ctx, "unitig_heads", n);
     hipLaunchKernelGGL((unitig_heads_kernel<NW>), dim3(uni_grid(n)), dim3(256), 0, ctx->stream, keys, (const ulonglong2 *)rk, n, shape, scan, dir);
   }
+  KMI_HIP(ctx, hipGetLastError());
+  out->tab = tab; out->mask = slots - 1u;
+  out->rk = rk; out->scan = scan; out->dir = dir; out->circ = circ;
+  return KMI_OK;
+}
+
+template <int NW>
+static kmi_status dbg_compact_impl(kmi_dbg *g, uint32_t t) {
+  kmi_ctx *ctx = g->ctx;
+  kmi_index *idx = g->nodes;
+  const KShape shape = g->shape;
+  const uint64_t n = idx->n_entries;
+  const uint32_t *occ = g->node_kind == KMI_DBG_EDGE_EXISTS ? nullptr : (const uint32_t *)idx->vals;
+  const uint64_t *keys = (const uint64_t *)idx->keys;
+  UniStages u;
+  KMI_TRY(uni_stages<NW>(g, t, &u));
+  ulonglong2 *rk = u.rk, *scan = u.scan, *sums = scan + n;
+  const uint8_t *dir = u.dir, *circ = u.circ;
+  const uint64_t n_tiles = (n + kUniScanTile - 1) / kUniScanTile;
   {
     ProfScope ps(ctx, "unitig_scan", n);
     hipLaunchKernelGGL(unitig_scan_tiles_kernel, dim3((uint32_t)n_tiles), dim3(kUniScanNT), 0, ctx->stream, (const ulonglong2 *)scan, n, sums);

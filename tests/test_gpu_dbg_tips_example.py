@@ -1,0 +1,75 @@
+"""examples/de_bruijn_tips.cpp through the facade (NodeIndex::spectrum, retain_counts, prune_edges, clip_tips, unitigs) on the
+cleaning pipeline's input: every printed count against tests/dbg_clean_model.py, tests/tips_model.py and tests/unitig_model.py on
+the oracle's node map. With min_count = 1 no node is filtered and the five end-of-read errors are there to clip; with the
+spectrum's valley as the threshold the filter has removed them already and the first round clips nothing."""
+import os
+import subprocess
+import tempfile
+
+import pytest
+
+from tests import dbg_clean_model as D
+from tests import oracle as orc
+from tests import tips_model as T
+from tests import unitig_model as M
+
+pytestmark = pytest.mark.gpu
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+
+
+def _valley(hist):
+    for c in range(1, len(hist) - 2):
+        if hist[c] < hist[c - 1] and hist[c] <= hist[c + 1]:
+            return c
+    return 1
+
+
+def _shape(nodes):
+    u = M.unitigs_from_strings(nodes)
+    return len(u), D.n50([len(x) for x, _, _ in u])
+
+
+def _expected(nodes, min_count, max_tip):
+    """the example's lines as (name, value) pairs, from the models"""
+    out = [("nodes_built", len(nodes))] + list(zip(("unitigs_built", "n50_built"), _shape(nodes)))
+    thr = min_count if min_count else _valley(D.spectrum(nodes, 256)[0])
+    kept = D.retain(nodes, thr, 2**32 - 1)
+    out += [("threshold", thr), ("erased", len(nodes) - len(kept))] + list(zip(("unitigs_filtered", "n50_filtered"), _shape(kept)))
+    cur, ps = D.prune(kept, 1)
+    out += [("cleared_pruned", ps["n_set_before"] - ps["n_set_after"])] + list(zip(("unitigs_pruned", "n50_pruned"), _shape(cur)))
+    r = 0
+    while True:
+        r += 1
+        cur, s = T.clip(cur, 1, max_tip)
+        cur, ps = D.prune(cur, 1)
+        out += [("r%d_candidates" % r, s["n_candidates"]), ("r%d_clipped" % r, s["n_tips_clipped"]), ("r%d_nodes_removed" % r, s["n_nodes_removed"]),
+                ("r%d_cleared" % r, ps["n_set_before"] - ps["n_set_after"])] + list(zip(("r%d_unitigs" % r, "r%d_n50" % r), _shape(cur)))
+        if s["n_tips_clipped"] == 0:
+            break
+    return out + [("rounds", r), ("nodes_final", len(cur))] + list(zip(("unitigs_final", "n50_final"), _shape(cur)))
+
+
+@pytest.mark.parametrize("args,rounds,final", [(["1"], 2, 19), (["1", "3"], 1, 29), ([], 1, 1)])
+def test_de_bruijn_tips_example(args, rounds, final):
+    k = 31
+    subprocess.check_call(["make", "-C", os.path.join(ROOT, "examples"), "de_bruijn_tips"], stdout=subprocess.DEVNULL)
+    exe = os.path.join(ROOT, "examples", "de_bruijn_tips")
+    genome, reads = D.pipeline_reads(k)
+    data = D.fastq(reads)
+    with tempfile.TemporaryDirectory() as d:
+        path = os.path.join(d, "reads.fastq")
+        with open(path, "wb") as f:
+            f.write(data)
+        out = subprocess.run([exe, path] + args, capture_output=True, text=True, timeout=300)
+    assert out.returncode == 0, out.stderr
+    got = [(line.split("\t")[0], int(line.split("\t")[1])) for line in out.stdout.splitlines() if "\t" in line]
+    s = orc.kspec(k)
+    om = orc.DbgMap(s)
+    om.insert(*orc.dbg_parse(s, data))
+    nodes = D.nodes_of(*om.export(canonical=True), k)
+    want = _expected(nodes, int(args[0]) if args else 0, int(args[1]) if len(args) > 1 else 2 * k)
+    assert got == want
+    vals = dict(got)
+    assert (vals["rounds"], vals["unitigs_final"]) == (rounds, final)
+    if args == ["1"]:   # the README's figures for this input
+        assert (vals["unitigs_pruned"], vals["n50_pruned"], vals["r1_clipped"], vals["r1_nodes_removed"], vals["n50_final"]) == (29, 115, 5, 30, 259)

@@ -21,7 +21,12 @@ of every old entry read whole (upper bound of what it fetches).
 Cleaning over ranks: N processes share the GPU over a gloo group as for --unitigs --ranks (staging through pinned host memory: not an
 interconnect); retain on every rank's share, kmi_dbg_prune_edges_dist_host timed warm, bytes exchanged per node, the slowest rank's
 wall time. Default input: 1 M reads of a 10 Mbp genome, k = 31.
-  python tools/dbg_bench.py --clean --ranks N [--rate R] [--out FILE] [reads] [genome] [k]"""
+  python tools/dbg_bench.py --clean --ranks N [--rate R] [--out FILE] [reads] [genome] [k]
+Tip clipping: the --clean input after retain_counts(2) and prune_edges(1); then rounds of clip_tips(1, 2 k) + prune_edges(1) until a
+round clips nothing (at most --rounds), each clip_tips timed once with its per-kernel times on a map whose workspace a first pass
+over the whole pipeline has warmed, with the stats, the unitig count and the N50 behind every round. The yardstick in the same run:
+kmi_dbg_compact on the map the first round runs on, whose table, links and jumping stages the call shares.
+  python tools/dbg_bench.py --tips [--rate R] [--rounds N] [reads] [genome] [k]"""
 import ctypes as C
 import os
 import sys
@@ -335,6 +340,87 @@ def main_clean(argv):
               % (compact_ms, name, moved, copy_ms, compact_ms / copy_ms))
 
 
+def main_tips(argv):
+    argv = list(argv)
+    rate = _flag(argv, "--rate", 0.005, float)
+    max_rounds = _flag(argv, "--rounds", 8, int)
+    n_reads = int(argv[0]) if len(argv) > 0 else 10_000_000
+    genome = int(argv[1]) if len(argv) > 1 else 100_000_000
+    k = int(argv[2]) if len(argv) > 2 else 31
+    host, n_err = with_substitutions(np.asarray(K.synth_fastq(seed=2, genome_len=genome, n_reads=n_reads)), n_reads, rate)
+    dev = torch.device("cuda", 0)
+    d = torch.from_numpy(host).to(dev)
+    ctx = K.Context(0, stream=torch.cuda.current_stream(dev).cuda_stream)
+    g = K.DeBruijnNodes(ctx, K.make_config(k))
+    print("clipping the tips of a de Bruijn node map, k=%d, %d reads over %d bp, %d substitutions (%.3g per base, seeded), after retain_counts(2) and "
+          "prune_edges(1); clip_tips(1, %d); one run on one GPU" % (k, n_reads, genome, n_err, rate, 2 * k))
+
+    def step(name, fn):
+        torch.cuda.synchronize()
+        ctx.profile_reset()
+        t0 = time.perf_counter()
+        r = fn()
+        torch.cuda.synchronize()
+        ms = (time.perf_counter() - t0) * 1e3
+        prof = {p["name"]: round(p["total_ms"], 3) for p in sorted(ctx.profile_get(), key=lambda p: -p["total_ms"]) if p["launches"]}
+        ctx.profile_reset()
+        print("%-28s %9.2f ms  %s" % (name, ms, prof), flush=True)
+        return r, ms, prof
+
+    for run in ("warm-up", "timed"):
+        g.clear(); g.build_device(d.data_ptr(), host.size)
+        g.retain_counts(2)
+        g.prune_edges(1)
+        torch.cuda.synchronize()
+        if run == "warm-up":   # the workspace and the pool reach their sizes
+            g.unitigs(1); g.clip_tips(1); g.prune_edges(1); g.unitigs(1)
+            continue
+        ctx.profile(True); ctx.profile_reset()
+        print("-- second build, every step timed once (wall time with the host's part, then the kernels' own times)")
+        n1 = g.local_size()
+        (off, _, _, _), cmp_ms, p_cmp = step("unitigs, before clipping", lambda: g.unitigs(1))
+        print("unitigs %-24s %10d, N50 %d, %d nodes" % ("before clipping", off.shape[0] - 1, _n50(off), n1))
+        first = None
+        for r in range(1, max_rounds + 1):
+            stats, ms, prof = step("clip_tips(1, %d), round %d" % (2 * k, r), lambda: g.clip_tips(1))
+            first = first or (ms, prof, stats)
+            pst, _, _ = step("prune_edges(1), round %d" % r, lambda: g.prune_edges(1))
+            (off, _, _, _), _, _ = step("unitigs, round %d" % r, lambda: g.unitigs(1))
+            print("round %d: %s; pruning cleared %d; unitigs %d, N50 %d, %d nodes"
+                  % (r, stats, pst["n_set_before"] - pst["n_set_after"], off.shape[0] - 1, _n50(off), g.local_size()), flush=True)
+            if stats["n_tips_clipped"] == 0:
+                break
+    ctx.profile(False)
+    ms, prof, stats = first
+    own = prof.get("tips_classify", float("nan")) + prof.get("tips_judge", float("nan"))
+    shared = sum(v for n, v in prof.items() if n.startswith("unitig_"))
+    shared_cmp = sum(v for n, v in p_cmp.items() if n in prof and n.startswith("unitig_"))
+    print("round 1 on %d nodes: clip_tips %.2f ms wall against kmi_dbg_compact %.2f ms wall; tips_classify %.3f + tips_judge %.3f = %.3f ms against "
+          "unitig_links %.3f ms (%.2f); the stages both run: %.3f ms in clip_tips, %.3f ms in kmi_dbg_compact; removal: tips_retain_count %.3f + "
+          "bucket_offsets %.3f + tips_retain_compact %.3f ms"
+          % (n1, ms, cmp_ms, prof.get("tips_classify", float("nan")), prof.get("tips_judge", float("nan")), own, p_cmp.get("unitig_links", float("nan")),
+             own / p_cmp.get("unitig_links", float("nan")), shared, shared_cmp, prof.get("tips_retain_count", float("nan")),
+             prof.get("bucket_offsets", float("nan")), prof.get("tips_retain_compact", float("nan"))))
+    # bytes the two kernels of the call's own touch, against a device-to-device copy of as many: classify reads per node the scan
+    # record (16) and writes the class (1); per head also the direction and circular flags (2), a ranking record (16) and two rows (64);
+    # judge reads every class (1). Candidates add a key, a lookup, a row and a junction word each: few, not counted.
+    nu = stats["n_unitigs"]
+    moved = n1 * (16 + 1 + 1) + nu * (2 + 16 + 64)
+    a = torch.empty(moved // 2, dtype=torch.uint8, device=dev)
+    b = torch.empty_like(a)
+    b.copy_(a)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(5):
+        b.copy_(a)
+    e1.record()
+    torch.cuda.synchronize()
+    copy_ms = e0.elapsed_time(e1) / 5
+    print("tips_classify + tips_judge %.3f ms; the bytes they touch (18 per node, 82 more per unitig): %d, device-to-device copy of as many %.3f ms "
+          "(mean of 5), ratio %.2f" % (own, moved, copy_ms, own / copy_ms))
+    g.close()
+
+
 def _clean_ranks_worker(rank, world, port, n_reads, genome, k, rate, ret):
     import torch.distributed as dist
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
@@ -410,6 +496,8 @@ def main():
         return main_clean_ranks(sys.argv[3:])
     if len(sys.argv) > 1 and sys.argv[1] == "--clean":
         return main_clean(sys.argv[2:])
+    if len(sys.argv) > 1 and sys.argv[1] == "--tips":
+        return main_tips(sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "--fasta":
         return main_fasta(sys.argv[2:])
     if len(sys.argv) > 3 and sys.argv[1] == "--unitigs" and sys.argv[2] == "--ranks":
