@@ -323,6 +323,15 @@ class NodeIndex {
     return s;
   }
 
+  // pop_bubbles: one round of bubble popping (kmi_dbg_pop_bubbles): of the unitigs that run between the same two junction ends, those
+  // of at most max_bubble_nodes nodes that have a greater sibling leave the map with both their junction counters. One rank only, as
+  // clip_tips.
+  kmi_dbg_pop_stats pop_bubbles(uint32_t min_edge_count = 1, uint32_t max_bubble_nodes = 2 * KmerType::size) {
+    kmi_dbg_pop_stats s{};
+    ::kmerind::check(ctx, kmi_dbg_pop_bubbles(g, min_edge_count, max_bubble_nodes, 0, &s));
+    return s;
+  }
+
   kmi_ctx *context() const { return ctx; }
 
  private:

@@ -966,6 +966,53 @@ typedef struct {
 kmi_status kmi_dbg_clip_tips(kmi_dbg *g, uint32_t min_edge_count, uint32_t max_tip_nodes, uint32_t flags,
                              kmi_dbg_clip_stats *stats /* may be NULL */);
 
+/* ---- popping bubbles: parallel unitigs between the same two junction ends (no counterpart in the reference)
+ * A substitution in the middle of a read that is seen often enough to pass the filter is not a dead end: it is a second path of
+ * about k nodes that leaves a junction and rejoins the true path k nodes later, and each such bubble cuts the true path into three
+ * unitigs and adds a fourth. kmi_dbg_pop_bubbles removes the lesser paths. With t = min_edge_count >= 1 and M = max_bubble_nodes
+ * >= 1; counters are read as the compaction reads them (0 / 1 for an EDGE_EXISTS map); everything is judged against the map AS IT
+ * WAS WHEN THE CALL BEGAN, so one call is one round and a pure function of the map:
+ *  1. Unitigs. Those of kmi_dbg_compact with threshold t. Cycles are never branches. Ends and their degrees are those of the tip
+ *     clipping's rule 1.
+ *  2. Branch. A path unitig X of any length is a branch when both its ends have degree exactly 1; for each end the neighbour w
+ *     behind that counter (the pruning's definition) is a node and not a node of X; for each end the reciprocal counter
+ *     (w, E', b') is >= t; and the two junction nodes w0 and w1 are different nodes. The two reciprocal counters are X's junction
+ *     counters and (w0, E0'), (w1, E1') its junction ends. A loop that leaves and re-enters one node is no branch.
+ *  3. Siblings, bubble. Branches with the same unordered pair of junction ends are siblings; a set of two or more siblings is a
+ *     bubble. Siblings differ in the base of their junction counter at either end: two counters of one end are two bases.
+ *  4. Key. With c0, c1 the values of X's two junction counters, read in the junction nodes, and b the base index of X's junction
+ *     counter at the junction node whose canonical k-mer is the smaller of the two (A < C < G < T, as the cycle cut compares
+ *     keys): key(X) = (min(c0, c1), max(c0, c1), -b), a total order within a bubble.
+ *  5. Verdict. A branch of at most M nodes is popped if and only if a sibling of any length has a greater key. So the greatest
+ *     branch of every bubble always stays; a branch longer than M can outweigh others but never leaves; of equal weights the
+ *     smaller base at the smaller junction node stays.
+ *  6. Effect, as in retain_counts and clip_tips. The nodes of the popped branches leave the map; both junction counters of every
+ *     popped branch are cleared, in nodes that stay; every other counter and every counts[8] keeps its value bit for bit; the
+ *     survivors keep their order, in fresh arrays of exactly the surviving size. When nothing leaves, the map stays as it is.
+ * Consequences. A junction end of a bubble has degree >= 2 and a branch's ends have degree 1, so a junction node never lies in a
+ * popped branch. On a map where prune_edges(t) clears nothing and no node is its own reverse complement (any odd k), a round
+ * leaves no counter that points at a removed node, and prune_edges(t) clears nothing on the result either; for even k the
+ * exemption of the pruning's rule 3 breaks that, as it does for tips. Tips and bubbles do not commute. The intended loop: clip_tips
+ * + prune_edges until nothing is clipped, then pop_bubbles + prune_edges until nothing is popped, then again from the top if the
+ * last pass removed anything.
+ * KMI_ERR_INVALID: t = 0; M = 0; any flag bit (none is defined: flags must be 0); an alphabet that is not 2-bit; a map that holds
+ * one rank's share of a build over ranks (a whole map built over a one-rank communicator is accepted). KMI_ERR_OVERFLOW: 2^31 - 1
+ * nodes or more. An empty map gives zeros. On any error the map holds what it held, and so does the result of an earlier
+ * compaction, and the stats are zeroed; a call that succeeds drops that result. The call is complete on return. There is NO form
+ * over ranks, for the tip clipping's reason. */
+typedef struct {
+  uint64_t n_nodes;            /* nodes of the map when the call began */
+  uint64_t n_unitigs;          /* unitigs of that map under t (paths and cycles): what kmi_dbg_compact(t) would report */
+  uint64_t n_branches;         /* rule 2 */
+  uint64_t n_bubbles;          /* sibling sets of two or more: the branches that have a sibling and no sibling with a greater key */
+  uint64_t n_popped;           /* branches removed by rule 5 */
+  uint64_t n_nodes_removed;
+  uint64_t n_counters_cleared; /* junction counters of popped branches, cleared in surviving nodes: 2 x n_popped */
+  uint64_t reserved;           /* 0 */
+} kmi_dbg_pop_stats;  /* 64 bytes */
+kmi_status kmi_dbg_pop_bubbles(kmi_dbg *g, uint32_t min_edge_count, uint32_t max_bubble_nodes, uint32_t flags,
+                               kmi_dbg_pop_stats *stats /* may be NULL */);
+
 /* ---- measurement support --------------------------------------------------- */
 /* per-kernel HIP-event timing on the context's stream (bench.py roofline leg) */
 kmi_status kmi_profile_enable(kmi_ctx *ctx, int on);

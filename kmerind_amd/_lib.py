@@ -68,6 +68,11 @@ class DbgClipStats(C.Structure):
 DBG_CLIP_ISLANDS = 1   # KMI_DBG_CLIP_ISLANDS
 
 
+class DbgPopStats(C.Structure):
+    _fields_ = [(f, C.c_uint64) for f in ("n_nodes", "n_unitigs", "n_branches", "n_bubbles", "n_popped", "n_nodes_removed",
+                                          "n_counters_cleared", "reserved")]
+
+
 class IndexOverlap(C.Structure):
     _fields_ = [("n_a", C.c_uint64), ("n_b", C.c_uint64), ("n_shared", C.c_uint64), ("sum_a", C.c_uint64), ("sum_b", C.c_uint64),
                 ("sum_a_shared", C.c_uint64), ("sum_b_shared", C.c_uint64), ("sum_min_shared", C.c_uint64)]
@@ -233,6 +238,7 @@ SIGNATURES = {
     "kmi_dbg_prune_edges": (C.c_int, [_P, _u32, C.POINTER(DbgPruneStats)]),
     "kmi_dbg_prune_edges_dist_host": (C.c_int, [_P, _P, _u32, C.POINTER(DbgPruneStats), C.POINTER(DbgPruneStats)]),
     "kmi_dbg_clip_tips": (C.c_int, [_P, _u32, _u32, _u32, C.POINTER(DbgClipStats)]),
+    "kmi_dbg_pop_bubbles": (C.c_int, [_P, _u32, _u32, _u32, C.POINTER(DbgPopStats)]),
     "kmi_dbg_compact": (C.c_int, [_P, _u32, C.POINTER(_u64), C.POINTER(_u64)]),
     "kmi_dbg_compact_dist_host": (C.c_int, [_P, _P, _u32, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
     "kmi_dbg_unitigs_export_host": (C.c_int, [_P, _P, _P, _P, _P, _sz, _sz]),

@@ -708,7 +708,7 @@ class DeBruijnNodes:
                                                        nu.value, nb.value))
         return offsets, bases[:nb.value], occ[:nu.value], circ[:nu.value].astype(bool)
 
-    # ---- cleaning the map on the device (kmi_dbg_spectrum_* / kmi_dbg_retain_counts / kmi_dbg_prune_edges* / kmi_dbg_clip_tips)
+    # ---- cleaning the map on the device (kmi_dbg_spectrum_* / kmi_dbg_retain_counts / kmi_dbg_prune_edges* / kmi_dbg_clip_tips / kmi_dbg_pop_bubbles)
     def spectrum(self, n_bins=256, comm=None):
         """(hist, totals) of the nodes' occurrence counts (counts[8]): hist[min(count, n_bins - 1)] counts the nodes
         (np.uint64[n_bins]); totals is a dict of n_entries, sum_counts, min_count, max_count. With `comm` the call is collective and
@@ -753,6 +753,16 @@ class DeBruijnNodes:
         s = L.DbgClipStats()
         self.ctx.check(lib.kmi_dbg_clip_tips(self.h, int(min_edge_count), m, L.DBG_CLIP_ISLANDS if islands else 0, C.byref(s)))
         return {f: getattr(s, f) for f, _ in L.DbgClipStats._fields_}
+
+    def pop_bubbles(self, min_edge_count=1, max_bubble_nodes=None):
+        """One round of bubble popping (kmi_dbg_pop_bubbles; the definition is in include/kmerind_hip.h): of the unitigs that run
+        between the same two junction ends, those of at most max_bubble_nodes nodes (None: 2 k) that have a greater sibling leave
+        the map, and both their junction counters are cleared -> dict of the kmi_dbg_pop_stats words. One rank only: a map that
+        holds a rank's share of a build over ranks is refused."""
+        m = 2 * int(self.cfg.k) if max_bubble_nodes is None else int(max_bubble_nodes)
+        s = L.DbgPopStats()
+        self.ctx.check(lib.kmi_dbg_pop_bubbles(self.h, int(min_edge_count), m, 0, C.byref(s)))
+        return {f: getattr(s, f) for f, _ in L.DbgPopStats._fields_}
 
     def unitig_sequences(self, min_edge_count=1, comm=None):
         """the sequences of unitigs() as a list of bytes, in unitig order"""

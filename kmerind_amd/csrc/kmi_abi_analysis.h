@@ -1,7 +1,7 @@
 // kmi_abi_analysis.h -- spectrum and retain, the de Bruijn node map's cleaning, compare / combine of two count indexes.
 //
-// Included by kmi_index.hip last (kmi_spectrum.h, kmi_dbg_clean.h, kmi_dbg_tips.h and kmi_setops.h hold what it calls; alone,
-// dist_check and dist_agree are kmi_index.hip's own).
+// Included by kmi_index.hip last (kmi_spectrum.h, kmi_dbg_clean.h, kmi_dbg_tips.h, kmi_dbg_bubbles.h and kmi_setops.h hold what it
+// calls; alone, dist_check and dist_agree are kmi_index.hip's own).
 #pragma once
 
 extern "C" {
@@ -124,6 +124,15 @@ kmi_status kmi_dbg_clip_tips(kmi_dbg *g, uint32_t min_edge_count, uint32_t max_t
   static_assert(sizeof(kmi_dbg_clip_stats) == 8 * sizeof(uint64_t), "eight words");
   uint64_t s[8];
   const kmi_status st = kmi::dbg_clip_tips(g, min_edge_count, max_tip_nodes, flags, s);
+  if (stats) memcpy(stats, s, sizeof(s));
+  return st;
+}
+
+kmi_status kmi_dbg_pop_bubbles(kmi_dbg *g, uint32_t min_edge_count, uint32_t max_bubble_nodes, uint32_t flags, kmi_dbg_pop_stats *stats) {
+  if (!g) return KMI_ERR_INVALID;
+  static_assert(sizeof(kmi_dbg_pop_stats) == 8 * sizeof(uint64_t), "eight words");
+  uint64_t s[8];
+  const kmi_status st = kmi::dbg_pop_bubbles(g, min_edge_count, max_bubble_nodes, flags, s);
   if (stats) memcpy(stats, s, sizeof(s));
   return st;
 }

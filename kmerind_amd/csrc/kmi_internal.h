@@ -67,6 +67,7 @@ enum WsSlot {
   WS_UNI_END,         // ... cycle candidates, then the end k-mer and end occurrences of every state
   WS_UNI_CNT,         // ... records per destination rank, cursors, device scalars
   WS_DBG_TIPS,        // tip clipping (kmi_dbg_tips.h): device scalars, survivors of every fine bucket, per-unitig junctions, per-node masks and classes
+  WS_DBG_BUBBLES,     // bubble popping (kmi_dbg_bubbles.h): the same, with two junctions per unitig and a verdict byte beside the class
   WS_LOOKUP_RECS,    // positional lookup / read profile (kmi_lookup.h): (key words, tag) records of the queries or of a batch's k-mers
   WS_LOOKUP_CNT,      // ... the looked-up count of every k-mer of a batch, in file order
   WS_SPECTRUM,        // count spectrum / count filter (kmi_spectrum.h): the call's device scalars, then the survivors of every fine bucket

@@ -26,7 +26,12 @@ Tip clipping: the --clean input after retain_counts(2) and prune_edges(1); then 
 round clips nothing (at most --rounds), each clip_tips timed once with its per-kernel times on a map whose workspace a first pass
 over the whole pipeline has warmed, with the stats, the unitig count and the N50 behind every round. The yardstick in the same run:
 kmi_dbg_compact on the map the first round runs on, whose table, links and jumping stages the call shares.
-  python tools/dbg_bench.py --tips [--rate R] [--rounds N] [reads] [genome] [k]"""
+  python tools/dbg_bench.py --tips [--rate R] [--rounds N] [reads] [genome] [k]
+Bubble popping: the map that --tips ends with; then rounds of pop_bubbles(1, 2 k) + prune_edges(1) until a round pops nothing (at
+most --rounds), each pop_bubbles timed once with its per-kernel times, with the stats, the unitig count and the N50 behind every
+round, and one tip round behind the last. The yardsticks in the same run: kmi_dbg_compact on the map the first round runs on, and a
+device-to-device copy of the bytes bubbles_classify and bubbles_judge touch.
+  python tools/dbg_bench.py --bubbles [--rate R] [--rounds N] [reads] [genome] [k]"""
 import ctypes as C
 import os
 import sys
@@ -421,6 +426,100 @@ def main_tips(argv):
     g.close()
 
 
+def main_bubbles(argv):
+    argv = list(argv)
+    rate = _flag(argv, "--rate", 0.005, float)
+    max_rounds = _flag(argv, "--rounds", 8, int)
+    n_reads = int(argv[0]) if len(argv) > 0 else 10_000_000
+    genome = int(argv[1]) if len(argv) > 1 else 100_000_000
+    k = int(argv[2]) if len(argv) > 2 else 31
+    host, n_err = with_substitutions(np.asarray(K.synth_fastq(seed=2, genome_len=genome, n_reads=n_reads)), n_reads, rate)
+    dev = torch.device("cuda", 0)
+    d = torch.from_numpy(host).to(dev)
+    ctx = K.Context(0, stream=torch.cuda.current_stream(dev).cuda_stream)
+    g = K.DeBruijnNodes(ctx, K.make_config(k))
+    print("popping the bubbles of a de Bruijn node map, k=%d, %d reads over %d bp, %d substitutions (%.3g per base, seeded), after retain_counts(2), "
+          "prune_edges(1) and the rounds of clip_tips(1, %d) + prune_edges(1) of --tips; pop_bubbles(1, %d); one run on one GPU"
+          % (k, n_reads, genome, n_err, rate, 2 * k, 2 * k))
+
+    def step(name, fn):
+        torch.cuda.synchronize()
+        ctx.profile_reset()
+        t0 = time.perf_counter()
+        r = fn()
+        torch.cuda.synchronize()
+        ms = (time.perf_counter() - t0) * 1e3
+        prof = {p["name"]: round(p["total_ms"], 3) for p in sorted(ctx.profile_get(), key=lambda p: -p["total_ms"]) if p["launches"]}
+        ctx.profile_reset()
+        print("%-28s %9.2f ms  %s" % (name, ms, prof), flush=True)
+        return r, ms, prof
+
+    for run in ("warm-up", "timed"):
+        g.clear(); g.build_device(d.data_ptr(), host.size)
+        g.retain_counts(2)
+        g.prune_edges(1)
+        for _ in range(max_rounds):   # the end state of --tips
+            clipped = g.clip_tips(1)["n_tips_clipped"]
+            g.prune_edges(1)
+            if clipped == 0:
+                break
+        torch.cuda.synchronize()
+        if run == "warm-up":   # the workspace and the pool reach their sizes
+            g.unitigs(1); g.pop_bubbles(1); g.prune_edges(1); g.unitigs(1)
+            continue
+        ctx.profile(True); ctx.profile_reset()
+        print("-- second build, every step timed once (wall time with the host's part, then the kernels' own times)")
+        n1 = g.local_size()
+        (off, _, _, _), cmp_ms, p_cmp = step("unitigs, before popping", lambda: g.unitigs(1))
+        print("unitigs %-24s %10d, N50 %d, %d nodes" % ("before popping", off.shape[0] - 1, _n50(off), n1))
+        first = None
+        for r in range(1, max_rounds + 1):
+            stats, ms, prof = step("pop_bubbles(1, %d), round %d" % (2 * k, r), lambda: g.pop_bubbles(1))
+            first = first or (ms, prof, stats)
+            pst, _, _ = step("prune_edges(1), round %d" % r, lambda: g.prune_edges(1))
+            (off, _, _, _), _, _ = step("unitigs, round %d" % r, lambda: g.unitigs(1))
+            print("round %d: %s; pruning cleared %d; unitigs %d, N50 %d, %d nodes"
+                  % (r, stats, pst["n_set_before"] - pst["n_set_after"], off.shape[0] - 1, _n50(off), g.local_size()), flush=True)
+            if stats["n_popped"] == 0:
+                break
+        tip, _, _ = step("clip_tips(1, %d), behind the popping" % (2 * k), lambda: g.clip_tips(1))
+        print("a tip round behind the popping: %s" % tip)
+    ctx.profile(False)
+    ms, prof, stats = first
+    nan = float("nan")
+    own = prof.get("bubbles_classify", nan) + prof.get("bubbles_judge", nan)
+    shared = sum(v for n, v in prof.items() if n.startswith("unitig_"))
+    shared_cmp = sum(v for n, v in p_cmp.items() if n in prof and n.startswith("unitig_"))
+    print("round 1 on %d nodes: pop_bubbles %.2f ms wall against kmi_dbg_compact %.2f ms wall; bubbles_classify %.3f + bubbles_judge %.3f = %.3f ms "
+          "against unitig_links %.3f ms (%.2f); the stages both run: %.3f ms in pop_bubbles, %.3f ms in kmi_dbg_compact; removal: tips_retain_count %.3f + "
+          "bucket_offsets %.3f + tips_retain_compact %.3f ms"
+          % (n1, ms, cmp_ms, prof.get("bubbles_classify", nan), prof.get("bubbles_judge", nan), own, p_cmp.get("unitig_links", nan),
+             own / p_cmp.get("unitig_links", nan), shared, shared_cmp, prof.get("tips_retain_count", nan), prof.get("bucket_offsets", nan),
+             prof.get("tips_retain_compact", nan)))
+    # bytes the two kernels of the call's own touch, against a device-to-device copy of as many. Per node: classify reads the scan record
+    # (16) and writes the class (1), judge reads the class (1) and writes the verdict (1). Per head: the direction and circular flags (2), a
+    # ranking record (16) and two rows (64). Per branch, classify: two end keys, two table probes (a slot and the key it names), the
+    # neighbours' ranking record and direction (17), their rows (32), two junctions written (16), two mask words (8); judge: the junctions
+    # (16), two rows (64), a mask word (4), the junction node's key, its own ranking record and direction (17), and for one sibling a
+    # probe, a ranking record and direction (17), a class (1) and two junctions (16)
+    nw, nu, nb = g.n_words, stats["n_unitigs"], stats["n_branches"]
+    per_branch = 2 * (8 * nw + 4 + 8 * nw + 17 + 32) + 16 + 8 + 16 + 64 + 4 + 8 * nw + 17 + (4 + 8 * nw + 17 + 1 + 16)
+    moved = n1 * (16 + 1 + 1 + 1) + nu * (2 + 16 + 64) + nb * per_branch
+    a = torch.empty(moved // 2, dtype=torch.uint8, device=dev)
+    b = torch.empty_like(a)
+    b.copy_(a)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(5):
+        b.copy_(a)
+    e1.record()
+    torch.cuda.synchronize()
+    copy_ms = e0.elapsed_time(e1) / 5
+    print("bubbles_classify + bubbles_judge %.3f ms; the bytes they touch (19 per node, 82 more per unitig, %d more per branch): %d, device-to-device "
+          "copy of as many %.3f ms (mean of 5), ratio %.2f" % (own, per_branch, moved, copy_ms, own / copy_ms))
+    g.close()
+
+
 def _clean_ranks_worker(rank, world, port, n_reads, genome, k, rate, ret):
     import torch.distributed as dist
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
@@ -498,6 +597,8 @@ def main():
         return main_clean(sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "--tips":
         return main_tips(sys.argv[2:])
+    if len(sys.argv) > 1 and sys.argv[1] == "--bubbles":
+        return main_bubbles(sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "--fasta":
         return main_fasta(sys.argv[2:])
     if len(sys.argv) > 3 and sys.argv[1] == "--unitigs" and sys.argv[2] == "--ranks":
