@@ -315,17 +315,23 @@ class NodeIndex {
   }
 
   // clip_tips: one round of tip clipping (kmi_dbg_clip_tips): dead-end unitigs of at most max_tip_nodes nodes that hang off a
-  // junction with a greater branch leave the map with their junction counters; flags: KMI_DBG_CLIP_ISLANDS. One rank only: there is
-  // no form over ranks, and a map that holds a rank's share of a build over ranks is refused (KMI_ERR_INVALID, thrown).
-  kmi_dbg_clip_stats clip_tips(uint32_t min_edge_count = 1, uint32_t max_tip_nodes = 2 * KmerType::size, uint32_t flags = 0) {
-    kmi_dbg_clip_stats s{};
-    ::kmerind::check(ctx, kmi_dbg_clip_tips(g, min_edge_count, max_tip_nodes, flags, &s));
-    return s;
+  // junction with a greater branch leave the map with their junction counters; flags: KMI_DBG_CLIP_ISLANDS. Returns the stats over
+  // all ranks (collective when the object holds a communicator: kmi_dbg_clip_tips_dist_host); local, if given, receives this rank's.
+  kmi_dbg_clip_stats clip_tips(uint32_t min_edge_count = 1, uint32_t max_tip_nodes = 2 * KmerType::size, uint32_t flags = 0,
+                               kmi_dbg_clip_stats *local = nullptr) {
+    kmi_dbg_clip_stats mine{}, total{};
+    if (rccl) ::kmerind::check(ctx, kmi_dbg_clip_tips_dist_host(g, rccl, min_edge_count, max_tip_nodes, flags, &mine, &total));   // collective
+    else {
+      ::kmerind::check(ctx, kmi_dbg_clip_tips(g, min_edge_count, max_tip_nodes, flags, &mine));
+      total = mine;
+    }
+    if (local) *local = mine;
+    return total;
   }
 
   // pop_bubbles: one round of bubble popping (kmi_dbg_pop_bubbles): of the unitigs that run between the same two junction ends, those
-  // of at most max_bubble_nodes nodes that have a greater sibling leave the map with both their junction counters. One rank only, as
-  // clip_tips.
+  // of at most max_bubble_nodes nodes that have a greater sibling leave the map with both their junction counters. One rank only:
+  // there is no form over ranks, and a map that holds a rank's share of a build over ranks is refused (KMI_ERR_INVALID, thrown).
   kmi_dbg_pop_stats pop_bubbles(uint32_t min_edge_count = 1, uint32_t max_bubble_nodes = 2 * KmerType::size) {
     kmi_dbg_pop_stats s{};
     ::kmerind::check(ctx, kmi_dbg_pop_bubbles(g, min_edge_count, max_bubble_nodes, 0, &s));

@@ -102,7 +102,8 @@ kmi_status kmi_ctx_reset_hints(kmi_ctx *ctx);
  * the context's last kmi_index_lookup_* / kmi_index_profile_reads_* / kmi_index_locate_* / kmi_index_seed_reads_* (1 when every
  * bucket's entries fit one table; 0: no bucket was looked at); 9: the entry count of the fullest bucket the context's last kmi_index_retain_counts / kmi_dbg_retain_counts met (0: the index was empty);
  * 10: the largest number of passes a bucket needed in the context's last kmi_index_compare* / kmi_index_combine (0: no bucket
- * was looked at); 13: bytes this rank sent in the context's last kmi_dbg_prune_edges_dist_host */
+ * was looked at); 13: bytes this rank sent in the context's last kmi_dbg_prune_edges_dist_host; 14: exchanges and 15: bytes this rank
+ * sent in the context's last kmi_dbg_clip_tips_dist_host, those of its unitig stages included */
 kmi_status kmi_ctx_debug_counter(const kmi_ctx *ctx, uint32_t which, uint64_t *value);
 /* A destroyed context leaves its large device blocks (workspace, spare index arrays: >= 1 MB each, 96 GB / 64 blocks at most) in a
  * process-wide cache per device, where the next context of that device finds them: its first build then does not wait for
@@ -950,8 +951,35 @@ kmi_status kmi_dbg_prune_edges_dist_host(kmi_dbg *g, kmi_comm *comm, uint32_t mi
  * KMI_ERR_INVALID: t = 0; M = 0; flag bits other than KMI_DBG_CLIP_ISLANDS; an alphabet that is not 2-bit; a map that holds one
  * rank's share of a build over ranks (as kmi_dbg_compact and kmi_dbg_prune_edges refuse it). KMI_ERR_OVERFLOW: 2^31 - 1 nodes or
  * more. An empty map gives zeros. On any error the map holds what it held, and so does the result of an earlier compaction; a call
- * that succeeds drops it. The call is complete on return. There is NO form over ranks: it needs the end records of the compaction
- * over ranks and a request / answer exchange like the pruning's. */
+ * that succeeds drops it, and the stats are zeroed on an error. The call is complete on return.
+ * _dist_host (collective): the graph is the union of the ranks' maps; rules 1-5 apply to that union unchanged, judged against the
+ * maps as they were when the call began, and the union afterwards is exactly what kmi_dbg_clip_tips gives on the whole map. Each
+ * rank keeps its surviving nodes in their order, rows bit for bit, in fresh arrays of the surviving size. A clipped tip's junction
+ * node usually lives on another rank than the tip's nodes, so a rank from which no node leaves can still have a counter cleared: it
+ * rewrites its rows; only a rank with nothing leaving and nothing cleared keeps its arrays. The protocol, after the stages of
+ * kmi_dbg_compact_dist_host up to its heads (which leave every node with its unitig's two end states and its distances to them):
+ *  - end degrees: per path unitig of at most M nodes each end state's owner sends the degree of its end to the other end's owner,
+ *    one record of 16 bytes, one exchange (a one-node unitig's record goes to its own rank);
+ *  - junction: the degree-1 end of a unitig whose other end is dead sends one request of (n_words + 2) x 8 bytes (the canonical
+ *    neighbour k-mer; its own state and the reciprocal counter; the unitig's identity, the smaller of its two end states) to the
+ *    owner of the neighbour, which applies rules 3 and 4 from its own rows and answers 16 bytes (state, candidate, clipped): two
+ *    exchanges;
+ *  - verdict: every node of a path unitig of at most M nodes asks the owners of both end states of its unitig, 16 bytes out and 16
+ *    back per end, two exchanges, and leaves when either says so. Nodes of longer unitigs and of cycles send nothing.
+ * stats_local: n_nodes, n_nodes_removed and n_counters_cleared count this rank's nodes and the counters cleared in them; n_unitigs
+ * the unitigs this rank owns by the ownership rule of kmi_dbg_compact_dist_host; n_islands / n_islands_removed count an island on the
+ * rank that holds the smaller of its two end states (rank << 32 | 2 * node + direction); n_candidates / n_tips_clipped count a
+ * candidate on the rank that holds its attached node, the one whose end has degree 1. stats_total: the sums over the ranks, the same
+ * on every rank. Either may be NULL. Refusals and limits are those of kmi_dbg_prune_edges_dist_host and of kmi_dbg_clip_tips:
+ * t = 0, M = 0, unknown flags, an alphabet that is not 2-bit, a communicator of another context and more than 256 ranks give
+ * KMI_ERR_INVALID on every rank alike, before anything collective; 2^31 - 1 or more nodes on a rank give KMI_ERR_OVERFLOW. A rank
+ * that fails on its own does not leave its peers waiting: the verdict is agreed on by an all-reduce before the first exchange,
+ * before each exchange that follows a step of the rank's own, and, with the fresh arrays filled, before the maps change -- all ranks
+ * swap or none does -- and the peers return KMI_ERR_PEER. On any error the map and an earlier compaction's result stay and the stats
+ * are zeroed; a call that succeeds drops that result on every rank, whether the rank lost a node or not. A one-rank communicator
+ * gives what kmi_dbg_clip_tips gives (with KMI_FORCE_DIST=1 through the code of several ranks, the rank being its own peer).
+ * kmi_dbg_clip_tips itself keeps refusing a rank's share. kmi_ctx_debug_counter 14 and 15 give the exchanges and the bytes this
+ * rank sent. */
 enum { KMI_DBG_CLIP_ISLANDS = 1u };
 typedef struct {
   uint64_t n_nodes;            /* nodes of the map when the call began */
@@ -965,6 +993,8 @@ typedef struct {
 } kmi_dbg_clip_stats;  /* 64 bytes */
 kmi_status kmi_dbg_clip_tips(kmi_dbg *g, uint32_t min_edge_count, uint32_t max_tip_nodes, uint32_t flags,
                              kmi_dbg_clip_stats *stats /* may be NULL */);
+kmi_status kmi_dbg_clip_tips_dist_host(kmi_dbg *g, kmi_comm *comm, uint32_t min_edge_count, uint32_t max_tip_nodes, uint32_t flags,
+                                       kmi_dbg_clip_stats *stats_local, kmi_dbg_clip_stats *stats_total);
 
 /* ---- popping bubbles: parallel unitigs between the same two junction ends (no counterpart in the reference)
  * A substitution in the middle of a read that is seen often enough to pass the filter is not a dead end: it is a second path of
@@ -999,7 +1029,8 @@ kmi_status kmi_dbg_clip_tips(kmi_dbg *g, uint32_t min_edge_count, uint32_t max_t
  * one rank's share of a build over ranks (a whole map built over a one-rank communicator is accepted). KMI_ERR_OVERFLOW: 2^31 - 1
  * nodes or more. An empty map gives zeros. On any error the map holds what it held, and so does the result of an earlier
  * compaction, and the stats are zeroed; a call that succeeds drops that result. The call is complete on return. There is NO form
- * over ranks, for the tip clipping's reason. */
+ * over ranks: the sibling matching spans two junctions on two ranks; it needs the stages and the request / answer exchanges of
+ * kmi_dbg_clip_tips_dist_host and a matching step of its own. */
 typedef struct {
   uint64_t n_nodes;            /* nodes of the map when the call began */
   uint64_t n_unitigs;          /* unitigs of that map under t (paths and cycles): what kmi_dbg_compact(t) would report */

@@ -744,15 +744,25 @@ class DeBruijnNodes:
             self.prune_totals = {f: getattr(s, f) for f in names}
         return {f: getattr(s, f) for f in names}
 
-    def clip_tips(self, min_edge_count=1, max_tip_nodes=None, islands=False):
+    def clip_tips(self, min_edge_count=1, max_tip_nodes=None, islands=False, comm=None):
         """One round of tip clipping (kmi_dbg_clip_tips; the definition is in include/kmerind_hip.h): dead-end unitigs of at most
         max_tip_nodes nodes (None: 2 k) that hang off a junction with a greater branch leave the map, and their junction counters
-        are cleared; islands=True also removes the short unitigs without any neighbour -> dict of the kmi_dbg_clip_stats words. One
-        rank only: a map that holds a rank's share of a build over ranks is refused."""
+        are cleared; islands=True also removes the short unitigs without any neighbour -> dict of the kmi_dbg_clip_stats words.
+        Without `comm` a map that holds a rank's share of a build over ranks is refused. With `comm` the call is collective over
+        the union of the ranks' maps (kmi_dbg_clip_tips_dist_host): the dict is this rank's and the sums over the ranks are left in
+        `self.clip_totals`."""
         m = 2 * int(self.cfg.k) if max_tip_nodes is None else int(max_tip_nodes)
+        names = [f for f, _ in L.DbgClipStats._fields_]
+        flags = L.DBG_CLIP_ISLANDS if islands else 0
         s = L.DbgClipStats()
-        self.ctx.check(lib.kmi_dbg_clip_tips(self.h, int(min_edge_count), m, L.DBG_CLIP_ISLANDS if islands else 0, C.byref(s)))
-        return {f: getattr(s, f) for f, _ in L.DbgClipStats._fields_}
+        if comm is not None:
+            tot = L.DbgClipStats()
+            self.ctx.check(lib.kmi_dbg_clip_tips_dist_host(self.h, comm.h, int(min_edge_count), m, flags, C.byref(s), C.byref(tot)))
+            self.clip_totals = {f: getattr(tot, f) for f in names}
+        else:
+            self.ctx.check(lib.kmi_dbg_clip_tips(self.h, int(min_edge_count), m, flags, C.byref(s)))
+            self.clip_totals = {f: getattr(s, f) for f in names}
+        return {f: getattr(s, f) for f in names}
 
     def pop_bubbles(self, min_edge_count=1, max_bubble_nodes=None):
         """One round of bubble popping (kmi_dbg_pop_bubbles; the definition is in include/kmerind_hip.h): of the unitigs that run

@@ -292,6 +292,8 @@ kmi_status kmi_ctx_debug_counter(const kmi_ctx *ctx, uint32_t which, uint64_t *v
     case 11: *value = (uint64_t)kmi::kSegCopyTile; return KMI_OK;
     case 12: *value = ctx->qd_answered; return KMI_OK;
     case 13: *value = ctx->prune_dist_bytes; return KMI_OK;
+    case 14: *value = ctx->tips_dist_exchanges; return KMI_OK;
+    case 15: *value = ctx->tips_dist_bytes; return KMI_OK;
     default: return KMI_ERR_INVALID;
   }
 }

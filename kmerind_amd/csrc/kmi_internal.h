@@ -239,6 +239,7 @@ struct kmi_ctx {
   uint32_t lookup_cap = 0;       // home slots of the tables of bucket_lookup_kernel, bucket_locate_*_kernel and the set operations (KMI_LOOKUP_CAP: tests reach the multi-pass code with a small index); 0: the table's own
   size_t profile_batch = (size_t)256 << 20;   // input bytes of a batch of kmi_index_profile_reads_* (KMI_PROFILE_BATCH)
   uint64_t lookup_npass = 0;     // the largest pass count a bucket used in the last lookup / profile / locate / seed_reads (kmi_ctx_debug_counter 8)
+  uint64_t tips_dist_exchanges = 0, tips_dist_bytes = 0;   // the last kmi_dbg_clip_tips_dist_host: exchanges, bytes this rank sent, stages included (kmi_ctx_debug_counter 14, 15)
   uint64_t prune_dist_bytes = 0;   // bytes this rank sent in the last kmi_dbg_prune_edges_dist_host (kmi_ctx_debug_counter 13)
   uint64_t retain_fullest = 0;   // entries of the fullest bucket the last kmi_index_retain_counts met (kmi_ctx_debug_counter 9)
   uint64_t setops_npass = 0;     // the largest pass count a bucket used in the last kmi_index_compare / kmi_index_combine (kmi_ctx_debug_counter 10)

@@ -546,13 +546,29 @@ static kmi_status ud_rank_rounds(UdRun &u, uint32_t bound) {
   return KMI_OK;
 }
 
+// what the stages up to the heads and their scan leave in the workspace, for kmi_dbg_compact_dist_host and for
+// kmi_dbg_clip_tips_dist_host (kmi_dbg_tips_dist.h), as UniStages of kmi_unitig.h does on one rank. Afterwards every node p knows
+// its unitig's two end states (rec[2p].succ and rec[2p + 1].succ, global), its distances to them (rec[..].dist, so the unitig has
+// rec[2p].dist + rec[2p + 1].dist + 1 nodes) and circ[p]; a head is the node with rec[2p + 1 - dir[p]].dist == 0.
+struct UdStages {
+  UdRun u;
+  uint32_t *tab; uint64_t slots;   // unitig_table of this rank's nodes
+  uint64_t *next, *endk;
+  uint8_t *dir, *circ;
+  ulonglong2 *scan;                // per node (unitig id, base offset), rank-local
+  uint64_t nu, nb;                 // this rank's unitigs and their bases
+};
+
+// links, ranking, cycle pass, ends, heads and scan. pre: what this rank found wrong on its own so far; it is agreed on, with the
+// workspace, before the first exchange
 template <int NW>
-static kmi_status dbg_compact_dist_impl(kmi_dbg *g, kmi_comm *comm, uint32_t t, kmi_status pre) {
+static kmi_status ud_stages(kmi_dbg *g, kmi_comm *comm, uint32_t t, kmi_status pre, UdStages *out) {
   kmi_ctx *ctx = g->ctx;
   kmi_index *idx = g->nodes;
   const KShape shape = g->shape;
   const bool exists = g->node_kind == KMI_DBG_EDGE_EXISTS;
-  UdRun u{};
+  UdRun &u = out->u;
+  u = UdRun{};
   u.g = g; u.comm = comm; u.ctx = ctx;
   u.p = comm_size(comm); u.me = (uint32_t)comm_rank(comm);
   u.n = (idx->has_data && pre == KMI_OK) ? idx->n_entries : 0; u.ns = 2u * u.n;
@@ -726,13 +742,29 @@ static kmi_status dbg_compact_dist_impl(kmi_dbg *g, kmi_comm *comm, uint32_t t, 
     KMI_HIP(ctx, hipMemcpyAsync(&tot, sums + n_tiles, sizeof(tot), hipMemcpyDeviceToHost, ctx->stream));
     KMI_HIP(ctx, hipStreamSynchronize(ctx->stream));
   }
-  const uint64_t nu = tot.x, nb = tot.y;
+  out->tab = tab; out->slots = slots; out->next = next; out->endk = endk; out->dir = dir; out->circ = circ; out->scan = scan;
+  out->nu = tot.x; out->nb = tot.y;
+  return KMI_OK;
+}
+
+template <int NW>
+static kmi_status dbg_compact_dist_impl(kmi_dbg *g, kmi_comm *comm, uint32_t t, kmi_status pre) {
+  kmi_ctx *ctx = g->ctx;
+  const KShape shape = g->shape;
+  UdStages s;
+  KMI_TRY(ud_stages<NW>(g, comm, t, pre, &s));
+  UdRun &u = s.u;
+  const uint64_t n = u.n, nu = s.nu, nb = s.nb;
+  const uint64_t *keys = (const uint64_t *)g->nodes->keys, *endk = s.endk;
+  const uint8_t *dir = s.dir, *circ = s.circ;
+  const ulonglong2 *scan = s.scan;
+  const ulonglong2 tot = make_ulonglong2(nu, nb);
 
   // ---- the result block (offsets[nu + 1], occurrences[nu], circular[nu], bases[nb]): agreed on before the last exchange
   const size_t off_b = (size_t)(nu + 1u) * 8u, occ_b = (size_t)nu * 8u, circ_b = ((size_t)nu + 15u) & ~(size_t)15u;
   const size_t bytes = off_b + occ_b + circ_b + (size_t)nb + 16u;
   void *buf = nullptr;
-  st = KMI_OK;
+  kmi_status st = KMI_OK;
   if (nu && pool_alloc(ctx, &buf, bytes) != hipSuccess) st = set_err(ctx, KMI_ERR_NOMEM, "hipMalloc failed for the unitigs");
   if (buf) { g->uni_buf = buf; g->uni_bytes = bytes; }
   KMI_TRY(dist_agree(comm, st));

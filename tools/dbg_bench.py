@@ -27,6 +27,14 @@ round clips nothing (at most --rounds), each clip_tips timed once with its per-k
 over the whole pipeline has warmed, with the stats, the unitig count and the N50 behind every round. The yardstick in the same run:
 kmi_dbg_compact on the map the first round runs on, whose table, links and jumping stages the call shares.
   python tools/dbg_bench.py --tips [--rate R] [--rounds N] [reads] [genome] [k]
+Tip clipping over ranks: N processes share the GPU over a gloo group as for --clean --ranks (staging through pinned host memory: the
+figures are device work plus host staging, not an interconnect), on its input after retain_counts(2) and prune_edges(1) over the
+ranks; then rounds of kmi_dbg_clip_tips_dist_host + prune_edges until a round clips nothing anywhere (at most --rounds), each timed
+once on a warmed workspace: wall on the slowest rank, the summed tips_dist_* kernel times of rank 0, exchanges, bytes exchanged per
+node, the stats. Beside them, in the same run, the one-rank kmi_dbg_clip_tips on the same graph (the ranks' reads in one buffer), round
+by round; the totals over the ranks must equal its stats in every round, or the run fails. Default input: 1 M reads of a 10 Mbp
+genome, k = 31.
+  python tools/dbg_bench.py --tips --ranks N [--rate R] [--rounds N] [--out FILE] [reads] [genome] [k]
 Bubble popping: the map that --tips ends with; then rounds of pop_bubbles(1, 2 k) + prune_edges(1) until a round pops nothing (at
 most --rounds), each pop_bubbles timed once with its per-kernel times, with the stats, the unitig count and the N50 behind every
 round, and one tip round behind the last. The yardsticks in the same run: kmi_dbg_compact on the map the first round runs on, and a
@@ -590,9 +598,135 @@ def main_clean_ranks(argv):
             f.write("\n")
 
 
+def _share_reads(rank, world, n_reads, genome, rate):
+    """the reads of one rank of the --clean / --tips inputs over ranks"""
+    lo, hi = n_reads * rank // world, n_reads * (rank + 1) // world
+    return with_substitutions(np.asarray(K.synth_fastq(seed=2, genome_len=genome, n_reads=hi - lo, first_read=lo)), hi - lo, rate, seed=11 + rank)[0]
+
+
+def _tips_ranks_worker(rank, world, port, n_reads, genome, k, rate, max_rounds, ret):
+    import torch.distributed as dist
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from kmerind_amd.transport import GroupComm
+        ctx = K.Context(0, rank=rank, nranks=world)
+        comm = GroupComm(ctx)
+        host = _share_reads(rank, world, n_reads, genome, rate)
+        g = K.DeBruijnNodes(ctx, K.make_config(k))
+        rounds = []
+        for run in ("warm-up", "timed"):
+            g.clear(); g.build_dist(host, comm)
+            g.retain_counts(2)
+            g.prune_edges(1, comm=comm)
+            for r in range(1, (1 if run == "warm-up" else max_rounds) + 1):   # (the warm-up: the workspace and the pool reach their sizes)
+                n_before = g.local_size()
+                ctx.profile(run == "timed"); ctx.profile_reset()
+                dist.barrier()
+                t0 = time.perf_counter()
+                stats = g.clip_tips(1, comm=comm)
+                wall = time.perf_counter() - t0
+                prof = {p["name"]: round(p["total_ms"], 3) for p in sorted(ctx.profile_get(), key=lambda p: -p["total_ms"]) if p["launches"]}
+                ctx.profile(False)
+                total = dict(g.clip_totals)
+                pst = g.prune_edges(1, comm=comm)
+                if run == "timed":
+                    rounds.append(dict(nodes=n_before, clip_ms=wall * 1e3, stats=stats, total=total, kernels_ms=prof, exchanges=ctx.debug_counter(14),
+                                       bytes_sent=ctx.debug_counter(15), pruned_behind=g.prune_totals["n_set_before"] - g.prune_totals["n_set_after"]))
+                if total["n_tips_clipped"] == 0:
+                    break
+        g.unitigs(1, comm=comm)
+        ret[rank] = dict(rounds=rounds, unitigs_total=g.unitig_totals[0], nodes_final=g.local_size())
+        g.close()
+        comm.close()
+        ctx.close()
+    finally:
+        dist.destroy_process_group()
+
+
+def main_tips_ranks(argv):
+    import json
+    import socket
+    import torch.multiprocessing as mp
+    argv = list(argv)
+    world = int(argv.pop(0))
+    rate = _flag(argv, "--rate", 0.005, float)
+    max_rounds = _flag(argv, "--rounds", 8, int)
+    out_path = _flag(argv, "--out", None, str)
+    n_reads = int(argv[0]) if len(argv) > 0 else 1_000_000
+    genome = int(argv[1]) if len(argv) > 1 else 10_000_000
+    k = int(argv[2]) if len(argv) > 2 else 31
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    ret = mp.Manager().dict()
+    mp.spawn(_tips_ranks_worker, args=(world, port, n_reads, genome, k, rate, max_rounds, ret), nprocs=world, join=True)
+    res = [ret[r] for r in range(world)]
+    # the one-rank call on the same graph: the ranks' reads in one buffer, after the ranks' processes have left the GPU
+    host = np.concatenate([_share_reads(r, world, n_reads, genome, rate) for r in range(world)])
+    ctx = K.Context(0)
+    g = K.DeBruijnNodes(ctx, K.make_config(k))
+    one = []
+    for run in ("warm-up", "timed"):
+        g.clear(); g.build(host)
+        g.retain_counts(2)
+        g.prune_edges(1)
+        for r in range(1, (1 if run == "warm-up" else max_rounds) + 1):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            stats = g.clip_tips(1)
+            torch.cuda.synchronize()
+            ms = (time.perf_counter() - t0) * 1e3
+            g.prune_edges(1)
+            if run == "timed":
+                one.append(dict(clip_ms=ms, stats=stats))
+            if stats["n_tips_clipped"] == 0:
+                break
+    one_unitigs = g.unitigs(1)[0].shape[0] - 1
+    g.close()
+    ctx.close()
+    n_rounds = len(res[0]["rounds"])
+    assert n_rounds == len(one), "the ranks ran %d rounds, the one rank %d" % (n_rounds, len(one))
+    print("clipping tips over %d ranks (gloo transport, staging through pinned host memory: device work plus host staging, not an interconnect), k=%d, "
+          "%d reads over %d bp (%.3g substitutions per base), after retain_counts(2) and prune_edges(1); clip_tips(1, %d); every call timed once, warm"
+          % (world, k, n_reads, genome, rate, 2 * k))
+    rows = []
+    for i in range(n_rounds):
+        per = [r["rounds"][i] for r in res]
+        total = per[0]["total"]
+        for x in per:
+            assert x["total"] == total, "the totals differ between ranks in round %d" % (i + 1)
+        assert total == one[i]["stats"], "round %d: over ranks %s, one rank %s" % (i + 1, total, one[i]["stats"])
+        for f in total:
+            assert sum(x["stats"][f] for x in per) == total[f], (i + 1, f)
+        nodes = sum(x["nodes"] for x in per)
+        sent = sum(x["bytes_sent"] for x in per)
+        own = round(sum(v for n, v in per[0]["kernels_ms"].items() if n.startswith("tips_dist_")), 3)
+        rows.append(dict(round=i + 1, nodes=nodes, clip_ms_per_rank=[round(x["clip_ms"], 1) for x in per], clip_ms_slowest=round(max(x["clip_ms"] for x in per), 1),
+                         tips_dist_kernels_ms_rank0=own, kernels_ms_rank0=per[0]["kernels_ms"], exchanges=per[0]["exchanges"], bytes_exchanged=sent,
+                         bytes_per_node=round(sent / max(nodes, 1), 1), stats_total=total, stats_per_rank=[x["stats"] for x in per],
+                         pruned_behind=per[0]["pruned_behind"], one_rank_clip_ms=round(one[i]["clip_ms"], 2)))
+        print("round %d on %d nodes: kmi_dbg_clip_tips_dist_host %.1f ms on the slowest rank (%s), tips_dist_* kernels of rank 0 %.3f ms, %d exchanges, "
+              "%.1f bytes exchanged per node; one-rank kmi_dbg_clip_tips on the same graph %.2f ms; totals = one-rank stats: %s"
+              % (i + 1, nodes, rows[-1]["clip_ms_slowest"], rows[-1]["clip_ms_per_rank"], own, rows[-1]["exchanges"], rows[-1]["bytes_per_node"],
+                 one[i]["clip_ms"], total), flush=True)
+    assert res[0]["unitigs_total"] == one_unitigs, (res[0]["unitigs_total"], one_unitigs)
+    summary = dict(ranks=world, k=k, reads=n_reads, genome=genome, rate=rate, rounds=rows, unitigs_total_after=res[0]["unitigs_total"],
+                   nodes_after=sum(r["nodes_final"] for r in res), transport="gloo over pinned host staging (not an interconnect)")
+    print("unitigs afterwards: %d over the ranks, %d on one rank" % (res[0]["unitigs_total"], one_unitigs))
+    print(json.dumps(summary))
+    if out_path:
+        with open(out_path, "w") as f:
+            json.dump(summary, f, indent=1)
+            f.write("\n")
+
+
 def main():
     if len(sys.argv) > 3 and sys.argv[1] == "--clean" and sys.argv[2] == "--ranks":
         return main_clean_ranks(sys.argv[3:])
+    if len(sys.argv) > 3 and sys.argv[1] == "--tips" and sys.argv[2] == "--ranks":
+        return main_tips_ranks(sys.argv[3:])
     if len(sys.argv) > 1 and sys.argv[1] == "--clean":
         return main_clean(sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "--tips":
