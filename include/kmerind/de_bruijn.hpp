@@ -330,12 +330,18 @@ class NodeIndex {
   }
 
   // pop_bubbles: one round of bubble popping (kmi_dbg_pop_bubbles): of the unitigs that run between the same two junction ends, those
-  // of at most max_bubble_nodes nodes that have a greater sibling leave the map with both their junction counters. One rank only:
-  // there is no form over ranks, and a map that holds a rank's share of a build over ranks is refused (KMI_ERR_INVALID, thrown).
-  kmi_dbg_pop_stats pop_bubbles(uint32_t min_edge_count = 1, uint32_t max_bubble_nodes = 2 * KmerType::size) {
-    kmi_dbg_pop_stats s{};
-    ::kmerind::check(ctx, kmi_dbg_pop_bubbles(g, min_edge_count, max_bubble_nodes, 0, &s));
-    return s;
+  // of at most max_bubble_nodes nodes that have a greater sibling leave the map with both their junction counters. Returns the stats
+  // over all ranks (collective when the object holds a communicator: kmi_dbg_pop_bubbles_dist_host); local, if given, receives this
+  // rank's.
+  kmi_dbg_pop_stats pop_bubbles(uint32_t min_edge_count = 1, uint32_t max_bubble_nodes = 2 * KmerType::size, kmi_dbg_pop_stats *local = nullptr) {
+    kmi_dbg_pop_stats mine{}, total{};
+    if (rccl) ::kmerind::check(ctx, kmi_dbg_pop_bubbles_dist_host(g, rccl, min_edge_count, max_bubble_nodes, 0, &mine, &total));   // collective
+    else {
+      ::kmerind::check(ctx, kmi_dbg_pop_bubbles(g, min_edge_count, max_bubble_nodes, 0, &mine));
+      total = mine;
+    }
+    if (local) *local = mine;
+    return total;
   }
 
   kmi_ctx *context() const { return ctx; }

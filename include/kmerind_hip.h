@@ -103,7 +103,8 @@ kmi_status kmi_ctx_reset_hints(kmi_ctx *ctx);
  * bucket's entries fit one table; 0: no bucket was looked at); 9: the entry count of the fullest bucket the context's last kmi_index_retain_counts / kmi_dbg_retain_counts met (0: the index was empty);
  * 10: the largest number of passes a bucket needed in the context's last kmi_index_compare* / kmi_index_combine (0: no bucket
  * was looked at); 13: bytes this rank sent in the context's last kmi_dbg_prune_edges_dist_host; 14: exchanges and 15: bytes this rank
- * sent in the context's last kmi_dbg_clip_tips_dist_host, those of its unitig stages included */
+ * sent in the context's last kmi_dbg_clip_tips_dist_host, those of its unitig stages included; 16 and 17: the same for the context's
+ * last kmi_dbg_pop_bubbles_dist_host, and 18 and 19: the share of its unitig stages in them */
 kmi_status kmi_ctx_debug_counter(const kmi_ctx *ctx, uint32_t which, uint64_t *value);
 /* A destroyed context leaves its large device blocks (workspace, spare index arrays: >= 1 MB each, 96 GB / 64 blocks at most) in a
  * process-wide cache per device, where the next context of that device finds them: its first build then does not wait for
@@ -1028,9 +1029,37 @@ kmi_status kmi_dbg_clip_tips_dist_host(kmi_dbg *g, kmi_comm *comm, uint32_t min_
  * KMI_ERR_INVALID: t = 0; M = 0; any flag bit (none is defined: flags must be 0); an alphabet that is not 2-bit; a map that holds
  * one rank's share of a build over ranks (a whole map built over a one-rank communicator is accepted). KMI_ERR_OVERFLOW: 2^31 - 1
  * nodes or more. An empty map gives zeros. On any error the map holds what it held, and so does the result of an earlier
- * compaction, and the stats are zeroed; a call that succeeds drops that result. The call is complete on return. There is NO form
- * over ranks: the sibling matching spans two junctions on two ranks; it needs the stages and the request / answer exchanges of
- * kmi_dbg_clip_tips_dist_host and a matching step of its own. */
+ * compaction, and the stats are zeroed; a call that succeeds drops that result. The call is complete on return.
+ * _dist_host (collective): the graph is the union of the ranks' maps; rules 1-6 apply to that union unchanged, judged against the
+ * maps as they were when the call began, and the union afterwards is exactly what kmi_dbg_pop_bubbles gives on the whole map. Each
+ * rank keeps its surviving nodes in their order, rows bit for bit apart from the cleared junction counters, in fresh arrays of the
+ * surviving size. A junction node usually lives on another rank than the branch's nodes, so a rank from which no node leaves can
+ * still have a counter cleared: it rewrites its rows; only a rank with nothing leaving and nothing cleared keeps its arrays. The
+ * protocol, after the stages of kmi_dbg_compact_dist_host up to its heads (kmi_dbg_bubbles_dist.h has the record layouts); the
+ * IDENTITY END of a unitig is the smaller of its two end states (rank << 32 | 2 * node + direction):
+ *  - junction: every end of degree 1 of a path unitig of any length sends (n_words + 2) x 8 bytes (the canonical neighbour k-mer;
+ *    its own state and the reciprocal counter; the unitig's identity) to the owner of the neighbour, which applies rule 2 for that
+ *    end from its own rows and answers 16 bytes (junction node, counter, its value): two exchanges;
+ *  - pairing: the identity end asks the other end for its junction, 16 bytes out, (n_words + 3) x 8 back (the junction node's k-mer
+ *    travels: rule 4 asks which junction node has the smaller one): two exchanges. The branch is assembled at the identity end;
+ *  - matching: each branch goes to the owner of its junction node with the smaller k-mer, where its siblings arrive too,
+ *    (n_words + 2) x 8 bytes, and gets 16 bytes back (has a sibling, has a greater sibling): two exchanges;
+ *  - clears: a popped branch sends one 16-byte record to the owner of either junction node: one exchange;
+ *  - telling: every node of a path unitig of at most M nodes asks the owner of its identity end, 16 bytes out and 16 back: two
+ *    exchanges. Nodes of longer unitigs and of cycles send nothing.
+ * stats_local: n_nodes, n_nodes_removed and n_counters_cleared count this rank's nodes and the counters cleared in them; n_unitigs
+ * the unitigs this rank owns by the ownership rule of kmi_dbg_compact_dist_host; n_branches and n_popped count a branch on the rank
+ * that holds its identity end; n_bubbles counts a bubble on the rank that holds the junction node with the smaller k-mer of its two,
+ * where its greatest branch is judged. stats_total: the sums over the ranks, the same on every rank; each field equals the one-rank
+ * call's on the whole map. Either may be NULL. Refusals and limits are those of kmi_dbg_clip_tips_dist_host: t = 0, M = 0, any flag
+ * bit, an alphabet that is not 2-bit, a communicator of another context and more than 256 ranks give KMI_ERR_INVALID on every rank
+ * alike, before anything collective; 2^31 - 1 or more nodes on a rank give KMI_ERR_OVERFLOW. A rank that fails on its own does not
+ * leave its peers waiting: the verdict is agreed on by an all-reduce before the first exchange, before each exchange that follows a
+ * step of the rank's own, and, with the fresh arrays filled, before the maps change -- all ranks swap or none does -- and the peers
+ * return KMI_ERR_PEER. On any error the map and an earlier compaction's result stay and the stats are zeroed; a call that succeeds
+ * drops that result on every rank, whether the rank lost a node or not. A one-rank communicator gives what kmi_dbg_pop_bubbles
+ * gives (with KMI_FORCE_DIST=1 through the code of several ranks, the rank being its own peer). kmi_dbg_pop_bubbles itself keeps
+ * refusing a rank's share. kmi_ctx_debug_counter 16 and 17 give the exchanges and the bytes this rank sent, stages included. */
 typedef struct {
   uint64_t n_nodes;            /* nodes of the map when the call began */
   uint64_t n_unitigs;          /* unitigs of that map under t (paths and cycles): what kmi_dbg_compact(t) would report */
@@ -1043,6 +1072,8 @@ typedef struct {
 } kmi_dbg_pop_stats;  /* 64 bytes */
 kmi_status kmi_dbg_pop_bubbles(kmi_dbg *g, uint32_t min_edge_count, uint32_t max_bubble_nodes, uint32_t flags,
                                kmi_dbg_pop_stats *stats /* may be NULL */);
+kmi_status kmi_dbg_pop_bubbles_dist_host(kmi_dbg *g, kmi_comm *comm, uint32_t min_edge_count, uint32_t max_bubble_nodes, uint32_t flags,
+                                         kmi_dbg_pop_stats *stats_local, kmi_dbg_pop_stats *stats_total);
 
 /* ---- measurement support --------------------------------------------------- */
 /* per-kernel HIP-event timing on the context's stream (bench.py roofline leg) */

@@ -240,6 +240,7 @@ SIGNATURES = {
     "kmi_dbg_clip_tips": (C.c_int, [_P, _u32, _u32, _u32, C.POINTER(DbgClipStats)]),
     "kmi_dbg_clip_tips_dist_host": (C.c_int, [_P, _P, _u32, _u32, _u32, C.POINTER(DbgClipStats), C.POINTER(DbgClipStats)]),
     "kmi_dbg_pop_bubbles": (C.c_int, [_P, _u32, _u32, _u32, C.POINTER(DbgPopStats)]),
+    "kmi_dbg_pop_bubbles_dist_host": (C.c_int, [_P, _P, _u32, _u32, _u32, C.POINTER(DbgPopStats), C.POINTER(DbgPopStats)]),
     "kmi_dbg_compact": (C.c_int, [_P, _u32, C.POINTER(_u64), C.POINTER(_u64)]),
     "kmi_dbg_compact_dist_host": (C.c_int, [_P, _P, _u32, C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64), C.POINTER(_u64)]),
     "kmi_dbg_unitigs_export_host": (C.c_int, [_P, _P, _P, _P, _P, _sz, _sz]),

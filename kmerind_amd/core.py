@@ -764,15 +764,23 @@ class DeBruijnNodes:
             self.clip_totals = {f: getattr(s, f) for f in names}
         return {f: getattr(s, f) for f in names}
 
-    def pop_bubbles(self, min_edge_count=1, max_bubble_nodes=None):
+    def pop_bubbles(self, min_edge_count=1, max_bubble_nodes=None, comm=None):
         """One round of bubble popping (kmi_dbg_pop_bubbles; the definition is in include/kmerind_hip.h): of the unitigs that run
         between the same two junction ends, those of at most max_bubble_nodes nodes (None: 2 k) that have a greater sibling leave
-        the map, and both their junction counters are cleared -> dict of the kmi_dbg_pop_stats words. One rank only: a map that
-        holds a rank's share of a build over ranks is refused."""
+        the map, and both their junction counters are cleared -> dict of the kmi_dbg_pop_stats words. Without `comm` a map that
+        holds a rank's share of a build over ranks is refused. With `comm` the call is collective over the union of the ranks'
+        maps (kmi_dbg_pop_bubbles_dist_host): the dict is this rank's and the sums over the ranks are left in `self.pop_totals`."""
         m = 2 * int(self.cfg.k) if max_bubble_nodes is None else int(max_bubble_nodes)
+        names = [f for f, _ in L.DbgPopStats._fields_]
         s = L.DbgPopStats()
-        self.ctx.check(lib.kmi_dbg_pop_bubbles(self.h, int(min_edge_count), m, 0, C.byref(s)))
-        return {f: getattr(s, f) for f, _ in L.DbgPopStats._fields_}
+        if comm is not None:
+            tot = L.DbgPopStats()
+            self.ctx.check(lib.kmi_dbg_pop_bubbles_dist_host(self.h, comm.h, int(min_edge_count), m, 0, C.byref(s), C.byref(tot)))
+            self.pop_totals = {f: getattr(tot, f) for f in names}
+        else:
+            self.ctx.check(lib.kmi_dbg_pop_bubbles(self.h, int(min_edge_count), m, 0, C.byref(s)))
+            self.pop_totals = {f: getattr(s, f) for f in names}
+        return {f: getattr(s, f) for f in names}
 
     def unitig_sequences(self, min_edge_count=1, comm=None):
         """the sequences of unitigs() as a list of bytes, in unitig order"""

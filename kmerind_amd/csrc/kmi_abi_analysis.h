@@ -1,6 +1,6 @@
 // kmi_abi_analysis.h -- spectrum and retain, the de Bruijn node map's cleaning, compare / combine of two count indexes.
 //
-// Included by kmi_index.hip last (kmi_spectrum.h, kmi_dbg_clean.h, kmi_dbg_tips.h, kmi_dbg_tips_dist.h, kmi_dbg_bubbles.h and kmi_setops.h hold what it
+// Included by kmi_index.hip last (kmi_spectrum.h, kmi_dbg_clean.h, kmi_dbg_tips.h, kmi_dbg_tips_dist.h, kmi_dbg_bubbles.h, kmi_dbg_bubbles_dist.h and kmi_setops.h hold what it
 // calls; alone, dist_check and dist_agree are kmi_index.hip's own).
 #pragma once
 
@@ -151,6 +151,23 @@ kmi_status kmi_dbg_pop_bubbles(kmi_dbg *g, uint32_t min_edge_count, uint32_t max
   uint64_t s[8];
   const kmi_status st = kmi::dbg_pop_bubbles(g, min_edge_count, max_bubble_nodes, flags, s);
   if (stats) memcpy(stats, s, sizeof(s));
+  return st;
+}
+
+kmi_status kmi_dbg_pop_bubbles_dist_host(kmi_dbg *g, kmi_comm *comm, uint32_t min_edge_count, uint32_t max_bubble_nodes, uint32_t flags,
+                                         kmi_dbg_pop_stats *stats_local, kmi_dbg_pop_stats *stats_total) {
+  if (!g) return KMI_ERR_INVALID;
+  if (stats_local) memset(stats_local, 0, sizeof(*stats_local));
+  if (stats_total) memset(stats_total, 0, sizeof(*stats_total));
+  KMI_TRY(dist_check(g->nodes, comm));
+  uint64_t sl[8], stt[8];
+  kmi_status st;
+  if (alone(g->ctx, comm)) {
+    st = kmi::dbg_pop_bubbles(g, min_edge_count, max_bubble_nodes, flags, sl);
+    memcpy(stt, sl, sizeof(sl));
+  } else st = kmi::dbg_pop_bubbles_dist(g, comm, min_edge_count, max_bubble_nodes, flags, sl, stt);
+  if (stats_local) memcpy(stats_local, sl, sizeof(sl));
+  if (stats_total) memcpy(stats_total, stt, sizeof(stt));
   return st;
 }
 

@@ -294,6 +294,10 @@ kmi_status kmi_ctx_debug_counter(const kmi_ctx *ctx, uint32_t which, uint64_t *v
     case 13: *value = ctx->prune_dist_bytes; return KMI_OK;
     case 14: *value = ctx->tips_dist_exchanges; return KMI_OK;
     case 15: *value = ctx->tips_dist_bytes; return KMI_OK;
+    case 16: *value = ctx->bubbles_dist_exchanges; return KMI_OK;
+    case 17: *value = ctx->bubbles_dist_bytes; return KMI_OK;
+    case 18: *value = ctx->bubbles_dist_stage_exchanges; return KMI_OK;
+    case 19: *value = ctx->bubbles_dist_stage_bytes; return KMI_OK;
     default: return KMI_ERR_INVALID;
   }
 }

@@ -38,8 +38,8 @@
 // ud_wave_slot; the masks hold four nodes a word (tips_set / tips_byte).
 //
 // Footprint per node beyond the stages: 7 bytes of per-state and per-node flags, 2 of masks; the request staging reuses the stages'
-// end k-mers. What bubble popping over ranks will want from here: td_round_trip (staged 16-byte questions to the owners of global
-// states, 16-byte answers back), the per-node removal kernels and td_swap.
+// end k-mers. What bubble popping over ranks (kmi_dbg_bubbles_dist.h) takes from here: td_round_trip (staged 16-byte questions to the
+// owners of global states, answers back), tips_dist_tell / tips_dist_gone, the per-node removal kernels and td_swap.
 //
 // Included by kmi_index.hip after kmi_unitig_dist.h and kmi_dbg_tips.h.
 #pragma once
@@ -273,8 +273,10 @@ static kmi_status td_exchange(UdRun &u, kmi_status mine, const void *send, const
 // those states; `answer` launches the kernel that writes one 16-byte answer per question that arrived (questions, their number,
 // answers); the answers return in arrival order: *got, *n_got. one_way: the questions are all there is (*got = what arrived).
 // pre: what this rank found wrong on its own since the last agreement
+// who: the call's name in the error texts; ans_bytes: the size of an answer (16, or wider: then `answer` and the caller read *got as words)
 template <typename Answer>
-static kmi_status td_round_trip(UdRun &u, kmi_status pre, uint64_t n_staged, Answer answer, bool one_way, const ulonglong2 **got, uint64_t *n_got) {
+static kmi_status td_round_trip(UdRun &u, const char *who, kmi_status pre, uint64_t n_staged, size_t ans_bytes, Answer answer, bool one_way, const void **got,
+                                uint64_t *n_got) {
   kmi_ctx *ctx = u.ctx;
   ulonglong2 *grouped = nullptr;
   std::vector<uint64_t> sc(u.p, 0), rc, rc2;
@@ -283,14 +285,14 @@ static kmi_status td_round_trip(UdRun &u, kmi_status pre, uint64_t n_staged, Ans
   kmi_status st = pre;
   if (st == KMI_OK) st = ud_group(u, n_staged, &grouped, sc);
   KMI_TRY(td_exchange(u, st, grouped, sc, sizeof(ulonglong2), WS_DIST_B, &p_req, rc, &n_req));
-  if (one_way) { *got = (const ulonglong2 *)p_req; *n_got = n_req; return KMI_OK; }
-  st = ws_get(ctx, WS_DIST_C, (size_t)(n_req + 8u) * sizeof(ulonglong2), &p_ans);
+  if (one_way) { *got = p_req; *n_got = n_req; return KMI_OK; }
+  st = ws_get(ctx, WS_DIST_C, (size_t)(n_req + 8u) * ans_bytes, &p_ans);
   if (st == KMI_OK && n_req) {
-    answer((const ulonglong2 *)p_req, n_req, (ulonglong2 *)p_ans);
-    if (hipGetLastError() != hipSuccess) st = set_err(ctx, KMI_ERR_DEVICE, "clip_tips: an answer kernel did not start");
+    answer((const ulonglong2 *)p_req, n_req, p_ans);
+    if (hipGetLastError() != hipSuccess) st = set_err(ctx, KMI_ERR_DEVICE, "%s: an answer kernel did not start", who);
   }
-  KMI_TRY(td_exchange(u, st, p_ans, rc, sizeof(ulonglong2), WS_DIST_D, &p_got, rc2, n_got));
-  *got = (const ulonglong2 *)p_got;
+  KMI_TRY(td_exchange(u, st, p_ans, rc, ans_bytes, WS_DIST_D, &p_got, rc2, n_got));
+  *got = p_got;
   return KMI_OK;
 }
 
@@ -363,7 +365,7 @@ static kmi_status dbg_clip_dist_impl(kmi_dbg *g, kmi_comm *comm, uint32_t t, uin
     hipLaunchKernelGGL(tips_dist_ends_kernel, dim3(uni_grid(ns)), dim3(256), 0, ctx->stream, edges, rec, (const uint8_t *)s.circ, ns, u.me, t, exists, max_nodes,
                        own, u.stage);
   }
-  st = td_round_trip(u, launched(), ns, [](const ulonglong2 *, uint64_t, ulonglong2 *) {}, true, &got, &n_got);
+  st = td_round_trip(u, "clip_tips", launched(), ns, sizeof(ulonglong2), [](const ulonglong2 *, uint64_t, void *) {}, true, (const void **)&got, &n_got);
   if (st != KMI_OK) return fail(st);
   if (n_got) {
     ProfScope ps(ctx, "tips_dist_ends_set", n_got);
@@ -425,10 +427,10 @@ static kmi_status dbg_clip_dist_impl(kmi_dbg *g, kmi_comm *comm, uint32_t t, uin
     hipLaunchKernelGGL(tips_dist_ask_kernel, dim3(uni_grid(ns)), dim3(256), 0, ctx->stream, rec, (const uint8_t *)s.circ, ns, u.me, max_nodes, u.stage);
   }
   if (st == KMI_OK) st = launched();
-  st = td_round_trip(u, st, ns, [&](const ulonglong2 *q, uint64_t n_q, ulonglong2 *a) {
+  st = td_round_trip(u, "clip_tips", st, ns, sizeof(ulonglong2), [&](const ulonglong2 *q, uint64_t n_q, void *a) {
     ProfScope ps(ctx, "tips_dist_tell", n_q);
-    hipLaunchKernelGGL(tips_dist_tell_kernel, dim3(uni_grid(n_q)), dim3(256), 0, ctx->stream, q, n_q, (const uint8_t *)verdict, ns, a);
-  }, false, &got, &n_got);
+    hipLaunchKernelGGL(tips_dist_tell_kernel, dim3(uni_grid(n_q)), dim3(256), 0, ctx->stream, q, n_q, (const uint8_t *)verdict, ns, (ulonglong2 *)a);
+  }, false, (const void **)&got, &n_got);
   if (st != KMI_OK) return fail(st);
   if (n_got) {
     ProfScope ps(ctx, "tips_dist_gone", n_got);

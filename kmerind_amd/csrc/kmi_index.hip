@@ -3679,6 +3679,7 @@ static kmi_status merge_impl(kmi_index *idx, uint32_t nparts, const uint64_t *ke
 #include "kmi_dbg_tips.h"
 #include "kmi_dbg_tips_dist.h"
 #include "kmi_dbg_bubbles.h"
+#include "kmi_dbg_bubbles_dist.h"
 #include "kmi_setops.h"
 
 struct kmi_comm;

@@ -67,7 +67,7 @@ enum WsSlot {
   WS_UNI_END,         // ... cycle candidates, then the end k-mer and end occurrences of every state
   WS_UNI_CNT,         // ... records per destination rank, cursors, device scalars
   WS_DBG_TIPS,        // tip clipping (kmi_dbg_tips.h): device scalars, survivors of every fine bucket, per-unitig junctions, per-node masks and classes
-  WS_DBG_BUBBLES,     // bubble popping (kmi_dbg_bubbles.h): the same, with two junctions per unitig and a verdict byte beside the class
+  WS_DBG_BUBBLES,     // bubble popping (kmi_dbg_bubbles.h): the same, with two junctions per unitig and a verdict byte beside the class; over ranks (kmi_dbg_bubbles_dist.h) junction words per state and a record index per counter
   WS_LOOKUP_RECS,    // positional lookup / read profile (kmi_lookup.h): (key words, tag) records of the queries or of a batch's k-mers
   WS_LOOKUP_CNT,      // ... the looked-up count of every k-mer of a batch, in file order
   WS_SPECTRUM,        // count spectrum / count filter (kmi_spectrum.h): the call's device scalars, then the survivors of every fine bucket
@@ -239,6 +239,8 @@ struct kmi_ctx {
   uint32_t lookup_cap = 0;       // home slots of the tables of bucket_lookup_kernel, bucket_locate_*_kernel and the set operations (KMI_LOOKUP_CAP: tests reach the multi-pass code with a small index); 0: the table's own
   size_t profile_batch = (size_t)256 << 20;   // input bytes of a batch of kmi_index_profile_reads_* (KMI_PROFILE_BATCH)
   uint64_t lookup_npass = 0;     // the largest pass count a bucket used in the last lookup / profile / locate / seed_reads (kmi_ctx_debug_counter 8)
+  uint64_t bubbles_dist_exchanges = 0, bubbles_dist_bytes = 0;   // the last kmi_dbg_pop_bubbles_dist_host: the same (kmi_ctx_debug_counter 16, 17)
+  uint64_t bubbles_dist_stage_exchanges = 0, bubbles_dist_stage_bytes = 0;   // ... of which its unitig stages' (18, 19)
   uint64_t tips_dist_exchanges = 0, tips_dist_bytes = 0;   // the last kmi_dbg_clip_tips_dist_host: exchanges, bytes this rank sent, stages included (kmi_ctx_debug_counter 14, 15)
   uint64_t prune_dist_bytes = 0;   // bytes this rank sent in the last kmi_dbg_prune_edges_dist_host (kmi_ctx_debug_counter 13)
   uint64_t retain_fullest = 0;   // entries of the fullest bucket the last kmi_index_retain_counts met (kmi_ctx_debug_counter 9)

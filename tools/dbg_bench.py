@@ -39,7 +39,14 @@ Bubble popping: the map that --tips ends with; then rounds of pop_bubbles(1, 2 k
 most --rounds), each pop_bubbles timed once with its per-kernel times, with the stats, the unitig count and the N50 behind every
 round, and one tip round behind the last. The yardsticks in the same run: kmi_dbg_compact on the map the first round runs on, and a
 device-to-device copy of the bytes bubbles_classify and bubbles_judge touch.
-  python tools/dbg_bench.py --bubbles [--rate R] [--rounds N] [reads] [genome] [k]"""
+  python tools/dbg_bench.py --bubbles [--rate R] [--rounds N] [reads] [genome] [k]
+Bubble popping over ranks: N processes share the GPU over a gloo group as for --tips --ranks (device work plus host staging, not an
+interconnect), on the graph that --tips --ranks ends with; then rounds of kmi_dbg_pop_bubbles_dist_host + prune_edges until a round
+pops nothing anywhere (at most --rounds), each timed once on a warmed workspace: wall on the slowest rank, the bubbles_dist_* kernel
+times and all kernel times of rank 0, exchanges and bytes exchanged per node, split into the unitig stages' share and the call's own,
+the stats. Beside them, in the same run, the one-rank kmi_dbg_pop_bubbles on the same graph, round by round; every field of the
+totals over the ranks must equal its stats in every round, or the run fails. Default input: 1 M reads of a 10 Mbp genome, k = 31.
+  python tools/dbg_bench.py --bubbles --ranks N [--rate R] [--rounds N] [--out FILE] [reads] [genome] [k]"""
 import ctypes as C
 import os
 import sys
@@ -722,11 +729,147 @@ def main_tips_ranks(argv):
             f.write("\n")
 
 
+def _bubbles_ranks_worker(rank, world, port, n_reads, genome, k, rate, max_rounds, ret):
+    import torch.distributed as dist
+    os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world))
+    dist.init_process_group("gloo", rank=rank, world_size=world)
+    try:
+        from kmerind_amd.transport import GroupComm
+        ctx = K.Context(0, rank=rank, nranks=world)
+        comm = GroupComm(ctx)
+        host = _share_reads(rank, world, n_reads, genome, rate)
+        g = K.DeBruijnNodes(ctx, K.make_config(k))
+        rounds = []
+        for run in ("warm-up", "timed"):
+            g.clear(); g.build_dist(host, comm)
+            g.retain_counts(2)
+            g.prune_edges(1, comm=comm)
+            for _ in range(max_rounds):   # the end state of --tips --ranks
+                g.clip_tips(1, comm=comm)
+                g.prune_edges(1, comm=comm)
+                if g.clip_totals["n_tips_clipped"] == 0:
+                    break
+            for r in range(1, (1 if run == "warm-up" else max_rounds) + 1):   # (the warm-up: the workspace and the pool reach their sizes)
+                n_before = g.local_size()
+                ctx.profile(run == "timed"); ctx.profile_reset()
+                dist.barrier()
+                t0 = time.perf_counter()
+                stats = g.pop_bubbles(1, comm=comm)
+                wall = time.perf_counter() - t0
+                prof = {p["name"]: round(p["total_ms"], 3) for p in sorted(ctx.profile_get(), key=lambda p: -p["total_ms"]) if p["launches"]}
+                ctx.profile(False)
+                total = dict(g.pop_totals)
+                sent = [ctx.debug_counter(i) for i in (16, 17, 18, 19)]
+                g.prune_edges(1, comm=comm)
+                if run == "timed":
+                    rounds.append(dict(nodes=n_before, pop_ms=wall * 1e3, stats=stats, total=total, kernels_ms=prof, exchanges=sent[0], bytes_sent=sent[1],
+                                       stage_exchanges=sent[2], stage_bytes_sent=sent[3],
+                                       pruned_behind=g.prune_totals["n_set_before"] - g.prune_totals["n_set_after"]))
+                if total["n_popped"] == 0:
+                    break
+        g.unitigs(1, comm=comm)
+        ret[rank] = dict(rounds=rounds, unitigs_total=g.unitig_totals[0], nodes_final=g.local_size())
+        g.close()
+        comm.close()
+        ctx.close()
+    finally:
+        dist.destroy_process_group()
+
+
+def main_bubbles_ranks(argv):
+    import json
+    import socket
+    import torch.multiprocessing as mp
+    argv = list(argv)
+    world = int(argv.pop(0))
+    rate = _flag(argv, "--rate", 0.005, float)
+    max_rounds = _flag(argv, "--rounds", 8, int)
+    out_path = _flag(argv, "--out", None, str)
+    n_reads = int(argv[0]) if len(argv) > 0 else 1_000_000
+    genome = int(argv[1]) if len(argv) > 1 else 10_000_000
+    k = int(argv[2]) if len(argv) > 2 else 31
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    ret = mp.Manager().dict()
+    mp.spawn(_bubbles_ranks_worker, args=(world, port, n_reads, genome, k, rate, max_rounds, ret), nprocs=world, join=True)
+    res = [ret[r] for r in range(world)]
+    # the one-rank call on the same graph: the ranks' reads in one buffer, after the ranks' processes have left the GPU
+    host = np.concatenate([_share_reads(r, world, n_reads, genome, rate) for r in range(world)])
+    ctx = K.Context(0)
+    g = K.DeBruijnNodes(ctx, K.make_config(k))
+    one = []
+    for run in ("warm-up", "timed"):
+        g.clear(); g.build(host)
+        g.retain_counts(2)
+        g.prune_edges(1)
+        for _ in range(max_rounds):
+            clipped = g.clip_tips(1)["n_tips_clipped"]
+            g.prune_edges(1)
+            if clipped == 0:
+                break
+        for r in range(1, (1 if run == "warm-up" else max_rounds) + 1):
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            stats = g.pop_bubbles(1)
+            torch.cuda.synchronize()
+            ms = (time.perf_counter() - t0) * 1e3
+            g.prune_edges(1)
+            if run == "timed":
+                one.append(dict(pop_ms=ms, stats=stats))
+            if stats["n_popped"] == 0:
+                break
+    one_unitigs = g.unitigs(1)[0].shape[0] - 1
+    g.close()
+    ctx.close()
+    n_rounds = len(res[0]["rounds"])
+    assert n_rounds == len(one), "the ranks ran %d rounds, the one rank %d" % (n_rounds, len(one))
+    print("popping bubbles over %d ranks (gloo transport, staging through pinned host memory: device work plus host staging, not an interconnect), k=%d, "
+          "%d reads over %d bp (%.3g substitutions per base), after retain_counts(2), prune_edges(1) and the rounds of clip_tips(1, %d) + prune_edges(1); "
+          "pop_bubbles(1, %d); every call timed once, warm" % (world, k, n_reads, genome, rate, 2 * k, 2 * k))
+    rows = []
+    for i in range(n_rounds):
+        per = [r["rounds"][i] for r in res]
+        total = per[0]["total"]
+        for x in per:
+            assert x["total"] == total, "the totals differ between ranks in round %d" % (i + 1)
+        assert total == one[i]["stats"], "round %d: over ranks %s, one rank %s" % (i + 1, total, one[i]["stats"])   # every field, every round
+        for f in total:
+            assert sum(x["stats"][f] for x in per) == total[f], (i + 1, f)
+        nodes = sum(x["nodes"] for x in per)
+        sent, staged = sum(x["bytes_sent"] for x in per), sum(x["stage_bytes_sent"] for x in per)
+        own = round(sum(v for n, v in per[0]["kernels_ms"].items() if n.startswith("bubbles_dist_")), 3)
+        every = round(sum(per[0]["kernels_ms"].values()), 3)
+        rows.append(dict(round=i + 1, nodes=nodes, pop_ms_per_rank=[round(x["pop_ms"], 1) for x in per], pop_ms_slowest=round(max(x["pop_ms"] for x in per), 1),
+                         bubbles_dist_kernels_ms_rank0=own, all_kernels_ms_rank0=every, kernels_ms_rank0=per[0]["kernels_ms"], exchanges=per[0]["exchanges"],
+                         stage_exchanges=per[0]["stage_exchanges"], bytes_exchanged=sent, stage_bytes_exchanged=staged,
+                         bytes_per_node=round(sent / max(nodes, 1), 1), stage_bytes_per_node=round(staged / max(nodes, 1), 1), stats_total=total,
+                         stats_per_rank=[x["stats"] for x in per], pruned_behind=per[0]["pruned_behind"], one_rank_pop_ms=round(one[i]["pop_ms"], 2)))
+        x = rows[-1]
+        print("round %d on %d nodes: kmi_dbg_pop_bubbles_dist_host %.1f ms on the slowest rank (%s); rank 0: bubbles_dist_* kernels %.3f ms, all kernels %.3f "
+              "ms; %d exchanges (%d the stages', %d the call's own), %.1f bytes exchanged per node (%.1f the stages', %.1f the call's own); one-rank "
+              "kmi_dbg_pop_bubbles on the same graph %.2f ms; totals = one-rank stats: %s"
+              % (i + 1, nodes, x["pop_ms_slowest"], x["pop_ms_per_rank"], own, every, x["exchanges"], x["stage_exchanges"], x["exchanges"] - x["stage_exchanges"],
+                 x["bytes_per_node"], x["stage_bytes_per_node"], x["bytes_per_node"] - x["stage_bytes_per_node"], one[i]["pop_ms"], total), flush=True)
+    assert res[0]["unitigs_total"] == one_unitigs, (res[0]["unitigs_total"], one_unitigs)
+    summary = dict(ranks=world, k=k, reads=n_reads, genome=genome, rate=rate, rounds=rows, unitigs_total_after=res[0]["unitigs_total"],
+                   nodes_after=sum(r["nodes_final"] for r in res), transport="gloo over pinned host staging (not an interconnect)")
+    print("unitigs afterwards: %d over the ranks, %d on one rank" % (res[0]["unitigs_total"], one_unitigs))
+    print(json.dumps(summary))
+    if out_path:
+        with open(out_path, "w") as f:
+            json.dump(summary, f, indent=1)
+            f.write("\n")
+
+
 def main():
     if len(sys.argv) > 3 and sys.argv[1] == "--clean" and sys.argv[2] == "--ranks":
         return main_clean_ranks(sys.argv[3:])
     if len(sys.argv) > 3 and sys.argv[1] == "--tips" and sys.argv[2] == "--ranks":
         return main_tips_ranks(sys.argv[3:])
+    if len(sys.argv) > 3 and sys.argv[1] == "--bubbles" and sys.argv[2] == "--ranks":
+        return main_bubbles_ranks(sys.argv[3:])
     if len(sys.argv) > 1 and sys.argv[1] == "--clean":
         return main_clean(sys.argv[2:])
     if len(sys.argv) > 1 and sys.argv[1] == "--tips":
